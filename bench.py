@@ -15,6 +15,13 @@ per GPU, each rank processes its own independent stereo stream (weak scaling,
 no collective on the data path; config-3 windows are below the landmark count
 at which the RCCL-sharded BA pays).  The barrier and the MAX over
 ranks of the timed region stay; value = frames of all ranks / that time.
+
+A plain run (bench.py --gpus 1 --steps N --warmup W) sets up, warms up, times
+the N steps and prints the headline result line.  --full adds every side
+measurement and check to that line (rooflines from profile steps and HIP-event
+timing of the dominant kernel family inside the timed region, batched MI,
+replica streams, the VO loop lines, sharded BA, CPU baselines, parity against
+the oracle).  --dump-outputs DIR writes the arrays the timed steps computed.
 """
 from __future__ import annotations
 
@@ -37,6 +44,18 @@ def parse():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every side measurement and check (profile steps and "
+                         "rooflines, event timing of the dominant family inside the timed region, batched MI, "
+                         "replica streams, the VO loop lines, sharded BA, StereoVisualOdometry, CPU baselines and "
+                         "parity against the oracle) and add them to the result line; without it the run sets up, "
+                         "warms up, times the steps and prints the headline fields only, and the options of "
+                         "those measurements have no effect")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed path left for each distinct frame it "
+                         "replayed to DIR/frame<k>_<name>.npy (rank 0): klt_pts, klt_status (float32), scale "
+                         "(float64: scale, iterations, stop), ba_cams, ba_pts (float64); the last timed step's "
+                         "frame is k = (steps - 1) %% frames.  Inputs depend on the arguments only")
     ap.add_argument("--frames", type=int, default=4, help="distinct synthetic frames cycled per rank")
     ap.add_argument("--ba-iters", type=int, default=10)
     ap.add_argument("--scale-iters", type=int, default=10,
@@ -91,7 +110,10 @@ def parse():
                          "config 3: ~40 of the 330 Schur launches, the frame rate ~1.3 %% below --timing none)")
     ap.add_argument("--profile-steps", type=int, default=3,
                     help="untimed steps with every family timed, to pick the dominant family")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 class FrameData:
@@ -413,6 +435,20 @@ def gpu_outputs(ctx, fd, sctx=None):
     cams, pts = fd.dba.download()
     return dict(klt=kp, klt_status=kst, scale=dict(stop=cs.stop.value, iterations=cs.it.value, scale=cs.sc.scale),
                 cams=cams, pts=pts, ba=dict(iterations=c.bs.iterations, successful_steps=c.bs.successful_steps))
+
+
+def dump_outputs(dirname, ctx, frames, steps, sctx=None):
+    """--dump-outputs: what the timed steps left for every distinct frame they
+    replayed (a replay always starts from the frame's own inputs, so a frame's
+    last replay is what any of its timed steps computed), one .npy per array."""
+    os.makedirs(dirname, exist_ok=True)
+    for k in range(min(steps, len(frames))):
+        g = gpu_outputs(ctx, frames[k], sctx)
+        s = g["scale"]
+        for name, a in (("klt_pts", g["klt"].astype(np.float32)), ("klt_status", g["klt_status"].astype(np.float32)),
+                        ("scale", np.array([s["scale"], s["iterations"], s["stop"]], np.float64)),
+                        ("ba_cams", np.asarray(g["cams"], np.float64)), ("ba_pts", np.asarray(g["pts"], np.float64))):
+            np.save(os.path.join(dirname, f"frame{k}_{name}.npy"), a)
 
 
 def compare(g, o):
@@ -1130,7 +1166,8 @@ def main():
     pool = pool1 = None
     model, ncpu, avail = host_cpu()
     cpu_workers = args.cpu_workers or min(16, avail)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    cpu_legs = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
+    if cpu_legs:
         # CPU legs: worker processes started before anything touches the GPU,
         # each pinned to its own core (1-thread leg: the first allowed core;
         # all-cores leg: the next cpu_workers cores)
@@ -1208,46 +1245,48 @@ def main():
         tctx.synchronize()
         ctx.synchronize()
         cu_split(False)
-    # untimed profile steps with every family timed: per-family device time and
-    # the dominant family (by device time) among those with a roofline
-    ctx.timing_reset()
-    ctx.timing(True)
-    pstats = new_stats()
-    for i in range(args.profile_steps):
-        gpu_step(ctx, frames[i % len(frames)], kp, ba_opts, pstats)
-    ctx.synchronize()
-    ctx.timing(False)
-    prof = {f: ctx.timing_read(f) for f in fam_names}
-    rl = {f: alg_work(f, cfg, frames) for f in fam_names if prof[f][0] > 0}
-    npf = max(1, pstats["frames"])
-    # per-frame device-time budget of every family (the latency-bound ones included)
-    budget = {f: {"launches_per_frame": round(prof[f][0] / npf, 2), "us_per_launch": round(1e3 * prof[f][1] / prof[f][0], 2),
-                  "us_per_frame": round(1e3 * prof[f][1] / npf, 1)} for f in fam_names if prof[f][0] > 0}
-    # the MI that runs in the frame (scale LM residual launches, speculative candidates included):
-    # 262 algorithmic bytes per executed track evaluation
-    mi_in_frame = None
-    if prof["SCALE_RES"][0] > 0:
-        b = 262.0 * cfg["n_feats"] * pstats["scale_executed"]
-        a_gbs = b / (prof["SCALE_RES"][1] * 1e-3) / 1e9
-        mi_in_frame = {"bound": "hbm", "achieved": round(a_gbs, 2), "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                       "frac": round(a_gbs / PEAK_HBM_GBS, 5), "kernel": "scale_res_ctrl_kernel",
-                       "track_evaluations_per_frame": round(cfg["n_feats"] * pstats["scale_executed"] / npf, 1),
-                       "us_per_frame": budget["SCALE_RES"]["us_per_frame"],
-                       # the whole persistent LM launch (control phases and waits included) per track evaluation
-                       "ns_per_track_evaluation": round(1e6 * prof["SCALE_RES"][1] /
-                                                        (cfg["n_feats"] * pstats["scale_executed"]), 2)}
-    # the persistent scale LM (one launch per frame) is the whole LM control loop with its
-    # phase waits, not one kernel's pass over its data: reported as mi_in_frame, not as the roofline kernel
-    persistent_scale = "SCALE_RES" in budget and budget["SCALE_RES"]["launches_per_frame"] <= 1.5
-    dom = max((f for f in rl if rl[f] is not None and not (f == "SCALE_RES" and persistent_scale)),
-              key=lambda f: prof[f][1])
-    # timed region: HIP events on the ctx stream around the dominant family only
-    ctx.timing_reset()
-    if args.timing != "none":
-        ctx.timing(True, None if args.timing == "all" else [dom])
-        # every k-th launch of the family: a live average over the timed region whose event
-        # records perturb the stream k times less (--timing-every 1: every launch)
-        ctx.timing_sample(args.timing_every)
+    if args.full:
+        # untimed profile steps with every family timed: per-family device time and
+        # the dominant family (by device time) among those with a roofline
+        ctx.timing_reset()
+        ctx.timing(True)
+        pstats = new_stats()
+        for i in range(args.profile_steps):
+            gpu_step(ctx, frames[i % len(frames)], kp, ba_opts, pstats)
+        ctx.synchronize()
+        ctx.timing(False)
+        prof = {f: ctx.timing_read(f) for f in fam_names}
+        rl = {f: alg_work(f, cfg, frames) for f in fam_names if prof[f][0] > 0}
+        npf = max(1, pstats["frames"])
+        # per-frame device-time budget of every family (the latency-bound ones included)
+        budget = {f: {"launches_per_frame": round(prof[f][0] / npf, 2),
+                      "us_per_launch": round(1e3 * prof[f][1] / prof[f][0], 2),
+                      "us_per_frame": round(1e3 * prof[f][1] / npf, 1)} for f in fam_names if prof[f][0] > 0}
+        # the MI that runs in the frame (scale LM residual launches, speculative candidates included):
+        # 262 algorithmic bytes per executed track evaluation
+        mi_in_frame = None
+        if prof["SCALE_RES"][0] > 0:
+            b = 262.0 * cfg["n_feats"] * pstats["scale_executed"]
+            a_gbs = b / (prof["SCALE_RES"][1] * 1e-3) / 1e9
+            mi_in_frame = {"bound": "hbm", "achieved": round(a_gbs, 2), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                           "frac": round(a_gbs / PEAK_HBM_GBS, 5), "kernel": "scale_res_ctrl_kernel",
+                           "track_evaluations_per_frame": round(cfg["n_feats"] * pstats["scale_executed"] / npf, 1),
+                           "us_per_frame": budget["SCALE_RES"]["us_per_frame"],
+                           # the whole persistent LM launch (control phases and waits included) per track evaluation
+                           "ns_per_track_evaluation": round(1e6 * prof["SCALE_RES"][1] /
+                                                            (cfg["n_feats"] * pstats["scale_executed"]), 2)}
+        # the persistent scale LM (one launch per frame) is the whole LM control loop with its
+        # phase waits, not one kernel's pass over its data: reported as mi_in_frame, not as the roofline kernel
+        persistent_scale = "SCALE_RES" in budget and budget["SCALE_RES"]["launches_per_frame"] <= 1.5
+        dom = max((f for f in rl if rl[f] is not None and not (f == "SCALE_RES" and persistent_scale)),
+                  key=lambda f: prof[f][1])
+        # timed region: HIP events on the ctx stream around the dominant family only
+        ctx.timing_reset()
+        if args.timing != "none":
+            ctx.timing(True, None if args.timing == "all" else [dom])
+            # every k-th launch of the family: a live average over the timed region whose event
+            # records perturb the stream k times less (--timing-every 1: every launch)
+            ctx.timing_sample(args.timing_every)
     stats = new_stats()
     cu_split(True)
     barrier()
@@ -1265,9 +1304,10 @@ def main():
     elapsed = time.perf_counter() - t_start
     cu_split(False)
     barrier()
-    ctx.timing(False)
-    ctx.timing_sample(1)
-    fams = {f: ctx.timing_read(f) for f in fam_names}
+    if args.full:
+        ctx.timing(False)
+        ctx.timing_sample(1)
+        fams = {f: ctx.timing_read(f) for f in fam_names}
     t_max = elapsed
     frames_total = stats["frames"]
     ba_total = stats["ba_iters"]
@@ -1280,6 +1320,47 @@ def main():
         dist.all_reduce(cnt)
         frames_total, ba_total = int(cnt[0].item()), int(cnt[1].item())
     value = frames_total / t_max
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctx, frames, args.steps, pipe.scale_ctx if pipe else None)
+    out = {
+        "metric": "frames/sec + BA iter/sec, 2000 feats x 20-keyframe window, 1/2/4/8 MI355X",
+        "value": round(value, 3),
+        "unit": "frames/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(1e3 * t_max / args.steps, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8+f32 (MI), f64 (BA)",
+        "data": "synthetic",
+        "config": {"workload": f"config {args.config}: {cfg['width']}x{cfg['height']} stereo, "
+                               f"{cfg['n_feats']} feats, {cfg['window']}-keyframe window, 11x11 MI patches",
+                   "frame": f"KLT + MI scale LM (LM, MAX_NB_ITER {args.scale_iters}, tolerances off) + "
+                            f"{args.ba_iters} BA LM iterations",
+                   "frame_kind": "composite: the three stages on independent synthetic inputs of the config's "
+                                 "shape (the connected VO loop is the `pipeline` line of --full)",
+                   "parallelism": f"{world} independent streams (one per GPU)",
+                   "pipeline": None if pipe is None else (
+                       ("front end (KLT + scale LM) of frame t+1 overlaps the BA of frame t" + (
+                           f" on disjoint CUs ({args.front_cus} of every 16 for the front end)"
+                           if 0 < args.front_cus < 16 else "")) if args.overlap == "frontend"
+                       else "KLT of frame t+1 overlaps the BA of frame t") +
+                       " (two HIP streams, event dependency per frame)"},
+        "ba_iter_per_s": round(ba_total / t_max, 2),
+        "scale_lm_per_frame": {k: round(stats[k2] / max(1, stats["frames"]), 3) for k, k2 in
+                               (("iterations", "scale_iters"), ("residual_evaluations", "scale_res_evals"),
+                                ("rejections", "scale_rejections"), ("executed_evaluations", "scale_executed"))},
+        "full": args.full,
+        "gen_s": round(gen_s, 1),
+    }
+    if not args.full:  # a plain run ends here: the headline fields only
+        if rank == 0:
+            print(json.dumps(out))
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     bound, amount, unit, peak = rl[dom]
     n_l, ms_l = fams[dom] if fams[dom][0] > 0 else prof[dom]
     if dom == "SCALE_RES":  # executed evaluations per launch (speculative candidate batches)
@@ -1373,35 +1454,7 @@ def main():
             pl_.close()
             pl_.join()
     if rank == 0:
-        out = {
-            "metric": "frames/sec + BA iter/sec, 2000 feats x 20-keyframe window, 1/2/4/8 MI355X",
-            "value": round(value, 3),
-            "unit": "frames/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(1e3 * t_max / args.steps, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8+f32 (MI), f64 (BA)",
-            "data": "synthetic",
-            "config": {"workload": f"config {args.config}: {cfg['width']}x{cfg['height']} stereo, "
-                                   f"{cfg['n_feats']} feats, {cfg['window']}-keyframe window, 11x11 MI patches",
-                       "frame": f"KLT + MI scale LM (LM, MAX_NB_ITER {args.scale_iters}, tolerances off) + "
-                                f"{args.ba_iters} BA LM iterations",
-                       "frame_kind": "composite: the three stages on independent synthetic inputs of the config's "
-                                     "shape (the connected VO loop is the `pipeline` line)",
-                       "parallelism": f"{world} independent streams (one per GPU)",
-                       "pipeline": None if pipe is None else (
-                           ("front end (KLT + scale LM) of frame t+1 overlaps the BA of frame t" + (
-                               f" on disjoint CUs ({args.front_cus} of every 16 for the front end)"
-                               if 0 < args.front_cus < 16 else "")) if args.overlap == "frontend" else "KLT of frame t+1 overlaps the BA of frame t") +
-                           " (two HIP streams, event dependency per frame)"},
-            "ba_iter_per_s": round(ba_total / t_max, 2),
-            "scale_lm_per_frame": {k: round(stats[k2] / max(1, stats["frames"]), 3) for k, k2 in
-                                   (("iterations", "scale_iters"), ("residual_evaluations", "scale_res_evals"),
-                                    ("rejections", "scale_rejections"), ("executed_evaluations", "scale_executed"))},
+        out.update({
             "parity": parity,
             "roofline": roofline,
             "mi_roofline": mi_rl,
@@ -1415,8 +1468,7 @@ def main():
             "kernel_ms_profile": {f: [prof[f][0], round(prof[f][1], 3)] for f in prof},
             "kernel_budget_per_frame": budget,
             "mi_in_frame": mi_in_frame,
-            "gen_s": round(gen_s, 1),
-        }
+        })
         print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()

@@ -1,6 +1,7 @@
 // Host test of the co-residency roster (uasl_motion_estimation_amd/csrc/roster.hpp):
 // the same protocol code the kernels run, over std atomics, with threads as
-// workgroups -- some dispatched late, after the decider's close.  Checks, for
+// workgroups -- some dispatched late, after the decider's close -- and the
+// launch's own clock for the bounded waits (no wall-clock time).  Checks, for
 // the three launch shapes that use it:
 //   persistent  (scale_lm_kernel): every workgroup joins, the first joiner
 //               decides; units of every phase dealt over the participants,
@@ -13,7 +14,6 @@
 // run nothing, nothing waits for a workgroup that has not joined, and the
 // count equals the on-time joins.  Exit status 0 = pass.
 #include <atomic>
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <thread>
@@ -22,6 +22,33 @@
 #include "../../uasl_motion_estimation_amd/csrc/roster.hpp"
 
 namespace {
+
+// The launch's clock.  Wall-clock windows make the outcome depend on the host's scheduler
+// (starting a thread can take longer than any window that keeps the test quick), so time
+// here is the launch's own: it stands still until every on-time workgroup of the launch has
+// arrived, and then moves only while the launch's decider (the workgroup whose bounded wait
+// the protocol is about) spins in Ops::pause().  A late workgroup does not sleep: it starts
+// once the event it is late for (the close, the steal) has happened.
+constexpr long long kTick = 1000;  // ticks per pause() of the decider
+std::atomic<long long> g_clock{0};
+std::atomic<bool> g_running{false};
+thread_local bool tl_decider = false;
+
+struct Launch {
+  explicit Launch(int on_time) : need(on_time) {
+    g_clock = 0;
+    g_running = need == 0;
+  }
+  void arrive() {
+    if (++arrived == need) g_running = true;
+  }
+  template <class Cond>
+  static void late_until(Cond happened) {
+    while (!happened()) std::this_thread::yield();
+  }
+  const int need;
+  std::atomic<int> arrived{0};
+};
 
 struct HostOps {
   static unsigned fetch_add(unsigned* p, unsigned v) { return __atomic_fetch_add(p, v, __ATOMIC_SEQ_CST); }
@@ -34,11 +61,11 @@ struct HostOps {
   }
   static unsigned load(const unsigned* p) { return __atomic_load_n(p, __ATOMIC_SEQ_CST); }
   static void store(unsigned* p, unsigned v) { __atomic_store_n(p, v, __ATOMIC_SEQ_CST); }
-  static long long now() {  // 100 MHz ticks, as s_memrealtime
-    return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch())
-               .count() / 10;
+  static long long now() { return g_clock.load(); }  // the launch's clock (ticks as the device's 100 MHz counter)
+  static void pause() {
+    if (tl_decider && g_running.load()) g_clock += kTick;
+    std::this_thread::yield();
   }
-  static void pause() { std::this_thread::yield(); }
 };
 
 int failures = 0;
@@ -51,8 +78,7 @@ int failures = 0;
     }                                     \
   } while (0)
 
-constexpr long long kWindow = 2000000;  // close window for the test: 20 ms (threads start within it)
-constexpr int kLateMs = 200;            // late workgroups start this long after the launch
+constexpr long long kWindow = 2000000;  // close window for the test, in ticks of the launch's clock
 
 // Persistent grid: G workgroups, `late` of them dispatched after the close.
 void persistent(int G, int late, int units, int phases) {
@@ -62,9 +88,13 @@ void persistent(int G, int late, int units, int phases) {
   for (auto& r : runs) r = 0;
   std::atomic<unsigned> arrivals{0};
   std::atomic<int> participants{0}, late_work{0};
+  Launch launch(G - late);
+  auto closed = [&]() { return (HostOps::load(roster) & me_roster::kClosed) != 0; };
   auto wg = [&](bool is_late) {
-    if (is_late) std::this_thread::sleep_for(std::chrono::milliseconds(kLateMs));
+    if (is_late) Launch::late_until(closed);
     int pid = me_roster::join<HostOps>(roster, (unsigned)G), np = 0;
+    tl_decider = pid == 0;
+    if (!is_late) launch.arrive();
     if (pid == 0)
       np = (int)me_roster::close<HostOps>(roster, (unsigned)G, kWindow);
     else if (pid > 0)
@@ -111,8 +141,12 @@ void workers(int nw, int late, int units, int steps, bool close_now, bool block0
   std::atomic<unsigned> step{0}, done{0};
   std::atomic<int> joined{0};
   int np0 = -1;
+  Launch launch(nw - late + (block0_late ? 0 : 1));
+  auto closed = [&]() { return (HostOps::load(roster) & me_roster::kClosed) != 0; };
   auto block0 = [&]() {
-    if (block0_late) std::this_thread::sleep_for(std::chrono::milliseconds(kLateMs));
+    if (block0_late) Launch::late_until(closed);  // the workers have given up on it
+    else launch.arrive();
+    tl_decider = true;
     np0 = me_roster::close<HostOps>(roster, (unsigned)nw, close_now ? 0 : kWindow);
     for (int J = 0; J < steps; ++J) {
       if (np0 == 0) {
@@ -133,9 +167,11 @@ void workers(int nw, int late, int units, int steps, bool close_now, bool block0
     step = 1u << 30;
   };
   auto worker = [&](bool is_late) {
-    if (is_late) std::this_thread::sleep_for(std::chrono::milliseconds(kLateMs));
+    if (is_late) Launch::late_until(closed);
     const int pid = me_roster::join<HostOps>(roster, 0u);
+    if (!is_late) launch.arrive();
     if (pid < 0) return;
+    tl_decider = block0_late;  // without block 0 the workers' own bounded wait decides
     const int np = me_roster::count_or_abandon<HostOps>(roster, kWindow * 2);
     if (pid >= np) return;  // abandoned: block 0 works alone
     joined++;
@@ -168,8 +204,11 @@ void assemblers(int na, int late, bool steal_now, bool block0_late = false) {
     for (auto& r : runs) r = 0;
     std::atomic<unsigned> cnt{0};
     std::atomic<bool> b0_done{false};
+    Launch launch(na - late + (block0_late ? 0 : 1));
     auto block0 = [&]() {
-      if (block0_late) std::this_thread::sleep_for(std::chrono::milliseconds(kLateMs));
+      if (block0_late) Launch::late_until([&]() { return cnt.load() >= (unsigned)(na - late); });
+      else launch.arrive();
+      tl_decider = true;
       const long long t0 = HostOps::now();
       while (cnt.load() < (unsigned)na && HostOps::now() - t0 < (steal_now ? 0 : kWindow)) HostOps::pause();
       if (cnt.load() < (unsigned)na)
@@ -189,11 +228,14 @@ void assemblers(int na, int late, bool steal_now, bool block0_late = false) {
       b0_done = true;
     };
     auto asmwg = [&](int u, bool is_late) {
-      if (is_late) std::this_thread::sleep_for(std::chrono::milliseconds(kLateMs));
-      if (!me_roster::claim<HostOps>(&words[u], gen)) return;
-      if (b0_done.load()) CHECK(false, "assemblers: unit %d claimed after block 0 went on", u);
-      runs[u]++;
-      cnt++;
+      if (is_late) Launch::late_until([&]() { return cnt.load() >= (unsigned)na; });  // after block 0's steal
+      const bool mine = me_roster::claim<HostOps>(&words[u], gen);
+      if (mine) {
+        if (b0_done.load()) CHECK(false, "assemblers: unit %d claimed after block 0 went on", u);
+        runs[u]++;
+        cnt++;
+      }
+      if (!is_late) launch.arrive();
     };
     std::vector<std::thread> th;
     th.emplace_back(block0);

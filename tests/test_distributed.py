@@ -500,7 +500,7 @@ def test_bench_world2_gloo_sharded_branch(tmp_path):
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--comm",
            "gloo", "--rank-device", "zero", "--steps", "2", "--warmup", "1", "--frames", "1", "--no-pipeline",
            "--pipeline-frames", "0", "--mi-pairs", "0", "--vo-matches", "0", "--sharded-reps", "1",
-           "--profile-steps", "1", "--no-cpu-baseline"]
+           "--profile-steps", "1", "--no-cpu-baseline", "--full"]
     r = subprocess.run(cmd, env=env, cwd=str(tmp_path), capture_output=True, text=True, timeout=110)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

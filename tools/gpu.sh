@@ -1,11 +1,12 @@
 #!/bin/bash
 # GPU-box steps (run through gpurun).  Every GPU step runs under its own time
 # limit, steps are chained with &&, and the first failure ends the call.
-#   tools/gpu.sh final                      GPU tests, smoke, default bench line (gpurun_out/final_*)
+#   tools/gpu.sh final                      GPU tests, smoke, the bench line with every side measurement
+#                                           (bench.py --full; the line goes to $ME_OUT_DIR, default out/)
 #   tools/gpu.sh prof TAG [BENCH ARGS]      rocprofv3 --kernel-trace --stats of the headline bench frame
 #                                           (no event timing) + FETCH_SIZE / WRITE_SIZE --pmc passes
 #                                           (gpurun_out/TAG/; summarise with tools/summarise.py kstats / pmc)
-#   tools/gpu.sh benchprof TAG              rocprofv3 --kernel-trace --stats of the full default bench command
+#   tools/gpu.sh benchprof TAG              rocprofv3 --kernel-trace --stats of bench.py --full (to $ME_OUT_DIR)
 #   tools/gpu.sh sq TAG KERNEL_RX UNITS UNIT -- CMD...
 #                                           SQ counter passes (one --pmc pass each) over CMD, summarised
 #                                           into profiles/TAG.txt / .json (tools/summarise.py sq)
@@ -20,12 +21,13 @@ set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 2
 mkdir -p gpurun_out
 R="$GRAFT_REPO_ROOT"
+O="${ME_OUT_DIR:-$R/out}"; mkdir -p "$O"
 cmd=$1; shift
 case "$cmd" in
   final)
     timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread > gpurun_out/final_tests.log 2>&1 && tail -3 gpurun_out/final_tests.log &&
     timeout -k 10 180 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > gpurun_out/final_smoke.log 2>&1 && tail -1 gpurun_out/final_smoke.log &&
-    timeout -k 10 400 python -u bench.py > gpurun_out/final_bench.json 2> gpurun_out/final_bench.err && tail -1 gpurun_out/final_bench.json | cut -c1-400
+    timeout -k 10 600 python -u bench.py --full > "$O/final_bench.json" 2> "$O/final_bench.err" && tail -1 "$O/final_bench.json" | cut -c1-400
     ;;
   prof)
     TAG=$1; shift
@@ -40,8 +42,8 @@ case "$cmd" in
   benchprof)
     TAG=$1
     cd /tmp && export TMPDIR=/tmp
-    timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$R/gpurun_out/$TAG/benchprof" -o run -- python3 "$R/bench.py" --no-cpu-baseline > "$R/gpurun_out/${TAG}_benchprof.log" 2>&1 &&
-    grep '^{' "$R/gpurun_out/${TAG}_benchprof.log" | cut -c1-300
+    timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$O/$TAG/benchprof" -o run -- python3 "$R/bench.py" --full --no-cpu-baseline > "$O/${TAG}_benchprof.log" 2>&1 &&
+    grep '^{' "$O/${TAG}_benchprof.log" | cut -c1-300
     ;;
   sq)
     TAG=$1; RX=$2; UNITS=$3; UNIT=$4; shift 4; [ "$1" = "--" ] && shift
