@@ -779,6 +779,21 @@ inline void calcOpticalFlowPyrLK(const amd::ImageView& prev, const amd::ImageVie
             "calcOpticalFlowPyrLK");
 }
 
+// Corner response of an 8-bit image (A12b, no reference counterpart: the
+// application's feature detector): rows x cols doubles, the KLT's minimum
+// eigenvalue of the win x win window centred on each pixel, 0 where the KLT
+// would reject the window (me_corner_response).  Feeds nonMaxSupScanline3x3.
+inline std::vector<double> cornerResponse(const amd::ImageView& img, int win = 21,
+                                          amd::Context& ctx = amd::Context::thread_default()) {
+  std::vector<double> out((size_t)img.rows * img.cols);
+  me_corner_params cp;
+  me_corner_default_params(&cp);
+  cp.win = win;
+  ctx.check(me_corner_response(ctx.get(), ME_HOST, img.data, img.cols, img.rows, img.step, &cp, out.data()),
+            "cornerResponse");
+  return out;
+}
+
 // The windowed stereo VO loop (me_vo_loop_*, csrc/vo_loop.hip): the
 // application loop the reference leaves to its caller -- per keyframe KLT,
 // epipolar MI matching, WBA_Point bookkeeping (feature_types.h:121-197),

@@ -95,7 +95,7 @@ int me_host_free(me_ctx* ctx, void* hptr);
    stream, so time only the families a measurement needs. */
 enum { ME_KT_MI = 0, ME_KT_SCALE_RES = 1, ME_KT_SCALE_NEQ = 2, ME_KT_BA_LINEARIZE = 3, ME_KT_BA_POINTS = 4,
        ME_KT_BA_SCHUR = 5, ME_KT_BA_SOLVE = 6, ME_KT_BA_STEP = 7, ME_KT_KLT = 8, ME_KT_PYR = 9, ME_KT_NMS = 10,
-       ME_KT_COUNT = 16, ME_KT_ALL = 0xffff };
+       ME_KT_CORNERS = 11, ME_KT_COUNT = 16, ME_KT_ALL = 0xffff };
 int me_timing_enable(me_ctx* ctx, int family_mask);
 int me_timing_read(me_ctx* ctx, int kernel, long* launches, double* total_ms);
 int me_timing_reset(me_ctx* ctx);
@@ -408,6 +408,9 @@ typedef struct {
   int has_velocity;
   int log_events;             /* keep the WBA_Point event log (me_vo_loop_events) */
   int async_enqueue;          /* window solves queued from a worker thread (ignored when ba == front) */
+  int detector;               /* new features of a keyframe: 0 grid (me_vo_new_cells), 1 corners (me_vo_new_corners) */
+  int corner_win;             /* me_corner_params of the corner detector (21, 1e-4) */
+  double corner_min_eig;
 } me_vo_loop_config;
 typedef struct {              /* pipeline.FrameResult */
   int t, n_tracked, n_new, n_active, n_window_pts, n_window_obs;
@@ -554,6 +557,41 @@ typedef struct { int win; int max_level; int max_iters; double eps; double min_e
 void me_klt_default_params(me_klt_params* p);
 int me_klt_track(me_ctx* ctx, me_mem mem, const uint8_t* prev, const uint8_t* next, int width, int height,
                  int stride, const float* pts_in, float* pts_out, uint8_t* status, int n, const me_klt_params* p);
+
+/* ---- A12b: corner detector (build-defined; no reference) ---------------
+ * Where the VO loop starts new tracks: the pixels that maximise the quantity
+ * the KLT tests before it accepts a window (the minimum eigenvalue of the
+ * structure tensor, klt.hip).  Response R(x, y), FP64, of an 8-bit image for
+ * an odd window `win` (3 <= win <= 31), half = (win - 1) / 2: dx, dy = the
+ * KLT's level-0 Scharr derivatives (3/10/3, reflect-101); A11 = sum dx^2,
+ * A12 = sum dx dy, A22 = sum dy^2 over the win x win pixels centred on
+ * (x, y), exact integers; a = (double)A * 2^-20;
+ *   R = (a22 + a11 - sqrt((a11 - a22) * (a11 - a22) + 4.0 * a12 * a12)) / (2.0 * win * win)
+ * where the KLT would accept the window at level 0 (x - half >= 0,
+ * y - half >= 0, x - half + win < width, y - half + win < height), else 0.0:
+ * at an integer position R is the KLT's own minEig, bit for bit.  Pixel p is
+ * a corner iff R(p) >= min_eig (> 0) and p beats its (up to) 8 neighbours
+ * inside the image in the total order "larger R first, then smaller
+ * row-major index y * width + x".  The definition is restated in numpy in
+ * uasl_motion_estimation_amd/corners.py (the checker). */
+typedef struct { int win; double min_eig; } me_corner_params;
+void me_corner_default_params(me_corner_params* p);              /* 21, 1e-4 */
+/* The response map (height x width doubles, row-major, no padding). */
+int me_corner_response(me_ctx* ctx, me_mem mem, const uint8_t* img, int width, int height, int stride,
+                       const me_corner_params* p, double* response);
+/* New features of a keyframe from the corners of img: the grid and the good
+   tracked features are those of me_vo_new_cells; a corner at integer (x, y)
+   with margin <= x < width - margin, margin <= y < height - margin (compared
+   as floats) belongs to the cell the same formula gives for (x, y); each cell
+   keeps its best corner in the order above; the first max(0, n_feats - #good)
+   cells in ascending order that are unoccupied and hold a corner emit
+   ((float)x, (float)y), lo = d_min; *out_count = their number.  n = 0 with
+   NULL uv / status / ok is allowed (the first keyframe).  Device memory,
+   asynchronous on the ctx stream, like me_vo_new_cells. */
+int me_vo_new_corners(me_ctx* ctx, const uint8_t* img, int width, int height, int stride, const float* uv,
+                      const uint8_t* status, const uint8_t* ok, int n, float margin, int nx, int ny, double cw,
+                      double ch, int n_feats, int d_min, const me_corner_params* p, float* out_uv, int32_t* out_lo,
+                      int32_t* out_count);
 
 /* ---- A11: non-maximum suppression ------------------------------------
  * Replaces std::vector<pt2D> me::nonMaxSupScanline3x3(const cv::Mat& input,

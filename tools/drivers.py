@@ -12,6 +12,9 @@ loads another build of libme_hip.so (tools/build_variant.sh).
   solve_ts               cam_solve_kernel phase stamps (a -DME_SOLVE_TS build), configs 3 and 5
   scale_ts [--front F]   persistent scale LM phase split (a -DME_SCALE_TS build)
   schur_stamps           pt_schur_kernel workgroup-0 stamps (a -DME_SCHUR_STAMPS build)
+  corners [--reps --loop N]
+                         corner detector kernels (1280x720, 3840x2160) and the config-3 native loop with
+                         detector 0 / 1, alternating
 """
 import argparse
 import ctypes
@@ -326,6 +329,111 @@ def cmd_schur_stamps(a):
               flush=True)
 
 
+def cmd_corners(a):
+    """The corner detector (csrc/corners.hip): me_corner_response and
+    me_vo_new_corners per launch (ME_KT_CORNERS events) at 1280x720 and
+    3840x2160 with 2000 tracked features on the config-3 grid, then (--loop N)
+    the native VO loop at config 3 over N keyframes with detector 0 and 1,
+    alternating, two repeats each."""
+    import math
+
+    import torch
+
+    from uasl_motion_estimation_amd import pipeline as PL
+    from uasl_motion_estimation_amd import synthetic as S
+    from uasl_motion_estimation_amd._lib import ME_DEVICE
+    from uasl_motion_estimation_amd.corners import corner_params
+    ctx = _setup(a.lib)
+    V = ctypes.c_void_p
+    out = {"note": "algorithmic bytes = w*h read + 8*w*h written (the map); the kernels stage, difference and sum "
+                   "in LDS and registers, so the expected bound is LDS / VALU, not HBM", "kernels": {}}
+    for W, H in ((1280, 720), (3840, 2160)):
+        _, fr = S.corridor_frames_torch(S.SEED0 + 3, W, H, 0, 1)
+        L = fr[0][0].contiguous()
+        torch.cuda.synchronize()
+        n, nf = 2000, 2000
+        aw, ah = W - 2 * PL.MARGIN, H - 2 * PL.MARGIN
+        nx = max(1, int(round(math.sqrt(nf * aw / ah))))
+        ny = max(1, int(math.ceil(nf / nx)))
+        cw, ch = aw / nx, ah / ny
+        rng = np.random.default_rng(0)
+        uv = np.stack([rng.uniform(PL.MARGIN, W - PL.MARGIN, n), rng.uniform(PL.MARGIN, H - PL.MARGIN, n)], -1)
+        d_map, d_uv, d_st, d_out = ctx.malloc(8 * W * H), ctx.malloc(8 * n), ctx.malloc(2 * n), ctx.malloc(16 + 12 * nf)
+        ctx.h2d(d_uv, uv.astype(np.float32))
+        st = np.ones(2 * n, np.uint8)
+        st[:n:8] = 0  # every 8th track lost: its cell is free unless another feature holds it
+        ctx.h2d(d_st, st)
+        p = corner_params()
+
+        def response():
+            ctx.check(ctx.lib.me_corner_response(ctx.h, ME_DEVICE, V(L.data_ptr()), W, H, W, ctypes.byref(p),
+                                                 V(d_map)), "me_corner_response")
+
+        def new_corners():
+            ctx.check(ctx.lib.me_vo_new_corners(ctx.h, V(L.data_ptr()), W, H, W, V(d_uv), V(d_st), V(d_st + n), n,
+                                                float(PL.MARGIN), nx, ny, cw, ch, nf, 2, ctypes.byref(p),
+                                                V(d_out + 16), V(d_out + 16 + 8 * nf), V(d_out)), "me_vo_new_corners")
+        for name, fn in (("me_corner_response", response), ("me_vo_new_corners", new_corners)):
+            for _ in range(5):
+                fn()
+            ctx.synchronize()
+            ctx.timing_reset()
+            ctx.timing(True, ["CORNERS"])
+            for _ in range(a.reps):
+                fn()
+            ctx.synchronize()
+            ctx.timing(False)
+            cnt, ms = ctx.timing_read("CORNERS")
+            us = 1000 * ms / max(cnt, 1)
+            gbs = 9 * W * H / (us * 1e-6) / 1e9
+            out["kernels"][f"{name} {W}x{H}"] = {"launches": cnt, "us_per_launch": round(us, 2),
+                                                 "algorithmic_GBps": round(gbs, 1),
+                                                 "fraction_of_8TBps": round(gbs / 8000, 4)}
+            print(f"{name} {W}x{H}: {us:.2f} us/launch over {cnt} launches, {gbs:.0f} GB/s algorithmic "
+                  f"({100 * gbs / 8000:.2f} % of 8 TB/s)", flush=True)
+        cnt = np.zeros(1, np.int32)
+        ctx.d2h(cnt, d_out)
+        out["kernels"][f"me_vo_new_corners {W}x{H}"]["emitted"] = int(cnt[0])
+        for d in (d_map, d_uv, d_st, d_out):
+            ctx.free(d)
+    if a.loop > 0:
+        c, N = 3, a.loop
+        arc = S.trajectory_arc(max(N, 2))
+        truth = [np.concatenate([t, S.R_to_aa_robust(R)]) for (R, t) in arc]
+        K = S.intrinsics(1280, 720)
+        frames = []
+        for c0 in range(0, N, 50):
+            _, fr = S.corridor_frames_torch(S.SEED0 + c, 1280, 720, c0, min(50, N - c0))
+            frames += [(Lk.contiguous(), Rk.contiguous()) for (Lk, Rk, _, _) in fr]
+            torch.cuda.synchronize()
+            print(f"rendered {len(frames)} keyframes", flush=True)
+        runs = []
+        for rep in range(-1, 2):  # (-1: a short untimed run, the first loop of a process pays the allocations)
+            for det in PL.DETECTORS:
+                cfg = PL.PipelineConfig.from_config(c, detector=det)
+                vo = PL.NativeStereoVO(cfg, ctx, K, truth[0], truth[1] - truth[0], log_events=False, overlap=True)
+                t0 = time.perf_counter()
+                for t in range(N if rep >= 0 else min(N, 30)):
+                    vo.process(t, *frames[t])
+                vo.finish()
+                dt = time.perf_counter() - t0
+                if rep < 0:
+                    vo.close()
+                    continue
+                st = vo._stats()
+                res = vo.results
+                vo.close()
+                names = ["klt_match", "first_match", "scale_submit", "window_submit", "ba_result", "scale_result"]
+                r = {"detector": det, "repeat": rep, "keyframes": N, "keyframes_per_s": round(N / dt, 2),
+                     "tracked_mean": round(float(np.mean([q.n_tracked for q in res[2:]])), 1),
+                     "new_mean": round(float(np.mean([q.n_new for q in res[2:]])), 1),
+                     "wait_ms_per_keyframe": {k: round(1e3 * st[3 + i] / N, 4) for i, k in enumerate(names)}}
+                runs.append(r)
+                print(json.dumps(r), flush=True)
+        out["loop_config3"] = runs
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--lib", default=os.environ.get("ME_LIB"))
@@ -351,6 +459,9 @@ def main():
     p.add_argument("--config", default="3")
     p = sub.add_parser("schur_stamps")
     p.add_argument("configs", nargs="?", default="3,4")
+    p = sub.add_parser("corners")
+    p.add_argument("--reps", type=int, default=200)
+    p.add_argument("--loop", type=int, default=200, help="keyframes of the config-3 native loop per run (0: skip)")
     a = ap.parse_args()
     globals()["cmd_" + a.cmd](a)
 

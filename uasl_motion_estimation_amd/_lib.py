@@ -37,7 +37,7 @@ ERRORS = {
 
 # kernel timing families (me_hip.h ME_KT_*)
 KT = dict(MI=0, SCALE_RES=1, SCALE_NEQ=2, BA_LINEARIZE=3, BA_POINTS=4, BA_SCHUR=5, BA_SOLVE=6, BA_STEP=7,
-          KLT=8, PYR=9, NMS=10)
+          KLT=8, PYR=9, NMS=10, CORNERS=11)
 
 
 class MEError(RuntimeError):
@@ -126,7 +126,7 @@ class VOLoopConfigC(ctypes.Structure):
                 ("scale_iters", c_int), ("fixed_frames", c_int), ("d_min", c_int), ("d_max", c_int),
                 ("baseline", c_double), ("feat_var", c_double), ("K", c_double * 9), ("first_pose", c_double * 6),
                 ("velocity", c_double * 6), ("has_velocity", c_int), ("log_events", c_int),
-                ("async_enqueue", c_int)]
+                ("async_enqueue", c_int), ("detector", c_int), ("corner_win", c_int), ("corner_min_eig", c_double)]
 
 
 class VOFrameResultC(ctypes.Structure):
@@ -143,6 +143,11 @@ VO_EVENT_DTYPE = np.dtype([("kind", np.int32), ("t", np.int32), ("id", np.int64)
 class KLTParamsC(ctypes.Structure):
     _fields_ = [("win", c_int), ("max_level", c_int), ("max_iters", c_int), ("eps", c_double),
                 ("min_eig", c_double)]
+
+
+class CornerParamsC(ctypes.Structure):
+    """me_corner_params (include/me_hip.h)."""
+    _fields_ = [("win", c_int), ("min_eig", c_double)]
 
 
 ALLREDUCE_FN = ctypes.CFUNCTYPE(c_int, POINTER(c_double), c_int, c_void_p)
@@ -162,6 +167,7 @@ EXPORTS = [
     "me_comm_unique_id", "me_comm_create_rccl", "me_comm_create_callback", "me_comm_destroy", "me_comm_info",
     "me_comm_allreduce", "me_comm_calibrate", "me_comm_exchange_us", "me_ba_shard_worthwhile_comm", "me_ba_solve_comm", "me_ba_shard_worthwhile", "me_ba_shard_exchange_us",
     "me_klt_default_params", "me_klt_track",
+    "me_corner_default_params", "me_corner_response", "me_vo_new_corners",
     "me_nms_scanline3x3",
     "me_vo_default_params", "me_vo_srand", "me_vo_rand", "me_vo_process",
     "me_mono_default_params", "me_mono_vo_process",
@@ -302,6 +308,11 @@ def load_library(path: str | None = None):
         "me_klt_default_params": (None, [P(KLTParamsC)]),
         "me_klt_track": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                  c_void_p, c_int, P(KLTParamsC)]),
+        "me_corner_default_params": (None, [P(CornerParamsC)]),
+        "me_corner_response": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, P(CornerParamsC), c_void_p]),
+        "me_vo_new_corners": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                      c_float, c_int, c_int, c_double, c_double, c_int, c_int, P(CornerParamsC),
+                                      c_void_p, c_void_p, c_void_p]),
         "me_nms_scanline3x3": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
                                        P(c_int)]),
         "me_vo_default_params": (None, [P(VOParamsC)]),

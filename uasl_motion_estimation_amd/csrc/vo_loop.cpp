@@ -3,7 +3,8 @@
 // The application loop around the hot path that pipeline.py's
 // WindowedStereoVO + GPUBackend run in Python, step for step in C++ over the
 // library's own entry points: KLT (me_klt_track), the epipolar MI matchers
-// (me_mi_epipolar_match / me_vo_new_cells / me_mi_epipolar_match_count), the
+// (me_mi_epipolar_match / me_vo_new_cells or, with cfg.detector = 1, the
+// corner detector me_vo_new_corners / me_mi_epipolar_match_count), the
 // scale LM (me_scale_optimise) and the sliding-window BA queued behind the
 // previous window (me_vo_window_submit / me_ba_wait_out).  The WBA_Point
 // bookkeeping (include/MotionEstimation/core/feature_types.h:121-197) is a
@@ -543,10 +544,14 @@ struct me_vo_loop {
     const int m = std::max(cfg.n_feats, 1);
     VL_TRY(dbuf("new", 16 + 17 * (size_t)m, &dn), "match");
     uint8_t* n8 = (uint8_t*)dn;
-    VL_TRY(me_vo_new_cells(tctx, (const float*)dres, r8 + 12 * (size_t)n, r8 + 13 * (size_t)n, n, cfg.width,
-                           cfg.height, (float)kMargin, nx, ny, cw, ch, cfg.n_feats, t, cfg.d_min,
-                           (float*)(n8 + 16), (int32_t*)(n8 + 16 + 12 * (size_t)m), (int32_t*)n8),
-           "me_vo_new_cells");
+    if (cfg.detector == 1) {
+      VL_TRY(new_corners(im, (const float*)dres, r8 + 12 * (size_t)n, r8 + 13 * (size_t)n, n, n8), "me_vo_new_corners");
+    } else {
+      VL_TRY(me_vo_new_cells(tctx, (const float*)dres, r8 + 12 * (size_t)n, r8 + 13 * (size_t)n, n, cfg.width,
+                             cfg.height, (float)kMargin, nx, ny, cw, ch, cfg.n_feats, t, cfg.d_min,
+                             (float*)(n8 + 16), (int32_t*)(n8 + 16 + 12 * (size_t)m), (int32_t*)n8),
+             "me_vo_new_cells");
+    }
     VL_TRY(me_mi_epipolar_match_count(tctx, im.L, im.R, cfg.width, cfg.height, cfg.width, (const float*)(n8 + 16),
                                       (const int32_t*)(n8 + 16 + 12 * (size_t)m), (const int32_t*)n8, m, nd_new,
                                       kPatch, cfg.d_max, 1, kRatio, (float)kMargin,
@@ -565,6 +570,41 @@ struct me_vo_loop {
     int k = *(const int32_t*)(h8 + o);
     k = std::max(0, std::min(k, m));
     const uint8_t* nb = h8 + o + 16;
+    nuv.assign((const float*)nb, (const float*)nb + 2 * (size_t)k);
+    nxr.assign((const float*)(nb + 8 * (size_t)m), (const float*)(nb + 8 * (size_t)m) + k);
+    nok.assign(nb + 16 * (size_t)m, nb + 16 * (size_t)m + k);
+    return ME_OK;
+  }
+  // The corner detector queued on the front end: tracked features in device memory (n = 0: none),
+  // new-feature block n8 (count (16 B) | uv | xr | lo | ok)
+  int new_corners(const Imgs& im, const float* uv, const uint8_t* st, const uint8_t* ok, int n, uint8_t* n8) {
+    const int m = std::max(cfg.n_feats, 1);
+    const me_corner_params cp{cfg.corner_win, cfg.corner_min_eig};
+    return me_vo_new_corners(tctx, im.L, cfg.width, cfg.height, cfg.width, n ? uv : nullptr, n ? st : nullptr,
+                             n ? ok : nullptr, n, (float)kMargin, nx, ny, cw, ch, cfg.n_feats, cfg.d_min, &cp,
+                             (float*)(n8 + 16), (int32_t*)(n8 + 16 + 12 * (size_t)m), (int32_t*)n8);
+  }
+  // A keyframe without tracked features under the corner detector: the detector and the new
+  // features' matcher in one submission (klt_match_new without its tracked half)
+  int corners_match(const Imgs& im, int nd_new, std::vector<float>& nuv, std::vector<float>& nxr,
+                    std::vector<uint8_t>& nok) {
+    void *dn, *ho;
+    const int m = std::max(cfg.n_feats, 1);
+    VL_TRY(dbuf("new", 16 + 17 * (size_t)m, &dn), "match");
+    uint8_t* n8 = (uint8_t*)dn;
+    VL_TRY(new_corners(im, nullptr, nullptr, nullptr, 0, n8), "me_vo_new_corners");
+    VL_TRY(me_mi_epipolar_match_count(tctx, im.L, im.R, cfg.width, cfg.height, cfg.width, (const float*)(n8 + 16),
+                                      (const int32_t*)(n8 + 16 + 12 * (size_t)m), (const int32_t*)n8, m, nd_new,
+                                      kPatch, cfg.d_max, 1, kRatio, (float)kMargin,
+                                      (float*)(n8 + 16 + 8 * (size_t)m), n8 + 16 + 16 * (size_t)m),
+           "me_mi_epipolar_match_count");
+    VL_TRY(hbuf("out", 16 + 17 * (size_t)m, &ho), "match");
+    VL_TRY(me_memcpy_async(tctx, ho, dn, 16 + 17 * (size_t)m), "match D2H");
+    VL_TRY(timed_wait(1, [&] { return me_synchronize(tctx); }), "corners_match");
+    const uint8_t* h8 = (const uint8_t*)ho;
+    int k = *(const int32_t*)h8;
+    k = std::max(0, std::min(k, m));
+    const uint8_t* nb = h8 + 16;
     nuv.assign((const float*)nb, (const float*)nb + 2 * (size_t)k);
     nxr.assign((const float*)(nb + 8 * (size_t)m), (const float*)(nb + 8 * (size_t)m) + k);
     nok.assign(nb + 16 * (size_t)m, nb + 16 * (size_t)m + k);
@@ -1073,6 +1113,8 @@ struct me_vo_loop {
         trk_uv.push_back(uv[2 * k + 1]);
         xr_trk.push_back(xr_all[k]);
       }
+    } else if (cfg.detector == 1) {
+      VL_TRY(corners_match(im, nd_new, nuv, nxr, nok), "corners_match");
     } else {
       new_cells_host(t, 0, nullptr, nuv);
       VL_TRY(match(im, nuv, nd_new, nxr, nok), "match");
@@ -1234,6 +1276,9 @@ void me_vo_loop_default_config(me_vo_loop_config* c) {
   const double K[9] = {f, 0, c->width / 2.0, 0, f, c->height / 2.0, 0, 0, 1};
   for (int k = 0; k < 9; ++k) c->K[k] = K[k];
   c->async_enqueue = 1;
+  c->detector = 0;
+  c->corner_win = 21;
+  c->corner_min_eig = 1e-4;
 }
 
 int me_vo_loop_create(me_ctx* ba, me_ctx* front, const me_vo_loop_config* cfg, me_vo_loop** out) {
@@ -1243,6 +1288,12 @@ int me_vo_loop_create(me_ctx* ba, me_ctx* front, const me_vo_loop_config* cfg, m
   if (cfg->width < 2 * kMargin + 1 || cfg->height < 2 * kMargin + 1 || cfg->n_feats <= 0 || cfg->window < 1 ||
       cfg->d_min < 0 || cfg->d_max < cfg->d_min || cfg->ba_iters < 0 || cfg->scale_iters < 0)
     return me_set_error(ba, ME_ERR_INVALID, "me_vo_loop_create: bad configuration");
+  if (cfg->detector != 0 && cfg->detector != 1)
+    return me_set_error(ba, ME_ERR_INVALID, "me_vo_loop_create: detector must be 0 (grid) or 1 (corners)");
+  if (cfg->detector == 1 &&
+      (cfg->corner_win < 3 || cfg->corner_win > 31 || !(cfg->corner_win & 1) || !(cfg->corner_min_eig > 0.0)))
+    return me_set_error(ba, ME_ERR_INVALID,
+                        "me_vo_loop_create: corner_win must be odd and in [3, 31], corner_min_eig > 0");
   auto v = std::make_unique<me_vo_loop>();
   v->ctx = ba;
   v->tctx = front;

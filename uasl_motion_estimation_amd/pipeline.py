@@ -52,6 +52,7 @@ ROCTX = os.environ.get("ME_ROCTX", "0") == "1"  # roctx ranges around the loop's
 PATCH = 11          # MI patch (11 x 11, window_size 5)
 W_SCALE = 5         # ScaleState::window_size
 MARGIN = 4 * W_SCALE + 4  # feature margin: every scale-LM ROI (incl. the +1 px NEQ patch) stays inside
+DETECTORS = ("grid", "corners")  # me_vo_loop_config.detector 0 / 1
 
 
 # ------------------------------------------------------------------ rotations (host, FP64)
@@ -120,6 +121,13 @@ class PipelineConfig:
     d_max: int = 128
     baseline: float = S.BASELINE
     feat_var: float = 0.25
+    detector: str = "grid"        # new features of a keyframe: "grid" (new_cells) or "corners" (corners.py)
+    corner_win: int = 21
+    corner_min_eig: float = 1e-4
+
+    def __post_init__(self):
+        if self.detector not in DETECTORS:
+            raise ValueError(f"detector must be one of {DETECTORS}")
 
     @staticmethod
     def from_config(c: int, **kw) -> "PipelineConfig":
@@ -235,9 +243,25 @@ class Backend:
     backend queues them (front end and BA on separate streams)."""
 
     d_max = 128
+    detector = ("grid", 21, 1e-4)  # (detector, corner_win, corner_min_eig) of the loop's configuration
 
     def frame_images(self, t: int, left: np.ndarray, right: np.ndarray):
         raise NotImplementedError
+
+    def new_features(self, t: int, imgs, uv_good: np.ndarray, grid, d_min: int = 0) -> np.ndarray:
+        """New features of keyframe t given the good tracked features
+        (uv_good, (n, 2) float32), (k, 2) float32.  On the host: new_cells for
+        the grid detector, the numpy restatement of the corner detector
+        (corners.new_corners_ref) on the host left image for "corners"."""
+        det, win, min_eig = self.detector
+        if det == "grid":
+            return new_cells(t, uv_good, grid)
+        from .corners import new_corners_ref
+
+        nx, ny, cw, ch, n_feats = grid
+        ones = np.ones(len(uv_good), np.uint8)
+        nuv, _ = new_corners_ref(imgs[3], uv_good, ones, ones, MARGIN, nx, ny, cw, ch, n_feats, d_min, win, min_eig)
+        return nuv
 
     def klt(self, prev, cur, pts: np.ndarray):
         """(n, 2) float32 -> (n, 2) float32, (n,) uint8 status."""
@@ -281,7 +305,7 @@ class Backend:
         uv, st, xr, ok = self.klt_match(h, imgs, lo, nd, dvalid)
         H, W = imgs[2]
         good = (st == 1) & in_margin(uv, W, H) & ok
-        nuv = new_cells(t, uv[good], grid)
+        nuv = self.new_features(t, imgs, uv[good], grid, d_min)
         nxr, nok = self.match(imgs, nuv, np.full(len(nuv), d_min, np.int64), nd_new, True)
         return uv, st, xr, ok, nuv, nxr, nok
 
@@ -628,9 +652,13 @@ class GPUBackend(Backend):
         # new-feature block: count (16 B) | uv (8 nf) | xr (4 nf) | lo (4 nf) | ok (nf)
         m = max(nf, 1)
         dn = self._dbuf("new", 16 + 17 * m)
-        c.check(c.lib.me_vo_new_cells(c.h, V(dres), V(dres + 12 * n), V(dres + 13 * n), n, W, H, float(MARGIN), nx,
-                                      ny, float(cw), float(ch), nf, t, d_min, V(dn + 16), V(dn + 16 + 12 * m), V(dn)),
-                "me_vo_new_cells")
+        if self.detector[0] == "corners":
+            self._new_corners(c, imgs, dres, dres + 12 * n, dres + 13 * n, n, grid, d_min, dn)
+        else:
+            c.check(c.lib.me_vo_new_cells(c.h, V(dres), V(dres + 12 * n), V(dres + 13 * n), n, W, H, float(MARGIN),
+                                          nx, ny, float(cw), float(ch), nf, t, d_min, V(dn + 16),
+                                          V(dn + 16 + 12 * m), V(dn)),
+                    "me_vo_new_cells")
         c.check(c.lib.me_mi_epipolar_match_count(c.h, V(imgs[0]), V(imgs[1]), W, H, W, V(dn + 16), V(dn + 16 + 12 * m),
                                                  V(dn), m, nd_new, PATCH, self.d_max, 1, 1.2, float(MARGIN),
                                                  V(dn + 16 + 8 * m), V(dn + 16 + 16 * m)),
@@ -649,6 +677,47 @@ class GPUBackend(Backend):
         nxr = self._view(ho, np.float32, k, o + 16 + 8 * m).copy()
         nok = self._view(ho, np.uint8, k, o + 16 + 16 * m).astype(bool)
         return uv, st, xr, ok, nuv, nxr, nok
+
+    def _new_corners(self, c, imgs, d_uv, d_status, d_ok, n, grid, d_min, dn):
+        """me_vo_new_corners queued on context c: tracked features in device
+        memory (n = 0: none), new-feature block dn (count | uv | xr | lo | ok)."""
+        import ctypes
+
+        from .corners import corner_params
+
+        nx, ny, cw, ch, nf = grid
+        H, W = imgs[2]
+        m = max(nf, 1)
+        V = ctypes.c_void_p
+        _, win, min_eig = self.detector
+        p = corner_params(win, min_eig)
+        c.check(c.lib.me_vo_new_corners(c.h, V(imgs[0]), W, H, W, V(d_uv) if n else None, V(d_status) if n else None,
+                                        V(d_ok) if n else None, n, float(MARGIN), nx, ny, float(cw), float(ch), nf,
+                                        d_min, ctypes.byref(p), V(dn + 16), V(dn + 16 + 12 * m), V(dn)),
+                "me_vo_new_corners")
+
+    def new_features(self, t, imgs, uv_good, grid, d_min=0):
+        """The corner detector on the device (me_vo_new_corners over the good
+        tracked features, uploaded); the grid detector stays on the host."""
+        if self.detector[0] != "corners":
+            return Backend.new_features(self, t, imgs, uv_good, grid, d_min)
+        n = len(uv_good)
+        c = self.mctx
+        m = max(grid[4], 1)
+        d_in = 0
+        if n:  # every given feature is good: status = ok = 1
+            hp = self._hbuf("nf_in", 10 * n)
+            self._view(hp, np.float32, 2 * n)[:] = np.asarray(uv_good, np.float32).ravel()
+            self._view(hp, np.uint8, 2 * n, 8 * n)[:] = 1
+            d_in = self._dbuf("nf_in", 10 * n)
+            c.copy_async(d_in, hp, 10 * n)
+        dn = self._dbuf("new", 16 + 17 * m)
+        self._new_corners(c, imgs, d_in, d_in + 8 * n, d_in + 9 * n, n, grid, d_min, dn)
+        ho = self._hbuf("nf_out", 16 + 8 * m)
+        c.copy_async(ho, dn, 16 + 8 * m)
+        c.synchronize()
+        k = int(self._view(ho, np.int32, 1)[0])
+        return self._view(ho, np.float32, 2 * k, 16).reshape(k, 2).copy()
 
     def match(self, imgs, uv, lo, nd, unique):
         n = len(uv)
@@ -929,6 +998,7 @@ class WindowedStereoVO:
         self.cfg = cfg
         self.be = backend
         self.be.d_max = cfg.d_max
+        self.be.detector = (cfg.detector, cfg.corner_win, cfg.corner_min_eig)
         if hasattr(backend, "reserve"):
             backend.reserve(cfg)
         self.K = np.asarray(S.intrinsics(cfg.width, cfg.height) if K is None else K, np.float64)
@@ -1127,7 +1197,7 @@ class WindowedStereoVO:
             self.active[act[~good]] = False
             trk_idx, trk_uv, xr = act[good], uv[good], xr_all[good]
         else:
-            nuv = new_cells(t, trk_uv, grid)
+            nuv = self.be.new_features(t, imgs, trk_uv, grid, cfg.d_min)
             nxr, nok = self._wait(self.be.match, imgs, nuv, np.full(len(nuv), cfg.d_min, np.int64), nd_new, True)
         # 6. frame t-1's scale LM queued now (front end, beside BA(t-1); its inputs are the lagged state,
         # untouched by this frame's bookkeeping): the GPU backend runs it on a worker thread
@@ -1432,6 +1502,8 @@ class NativeStereoVO:
             c.velocity[:] = [float(x) for x in np.asarray(velocity)]
         c.log_events = int(log_events)
         c.async_enqueue = int(async_enqueue)
+        c.detector = DETECTORS.index(cfg.detector)
+        c.corner_win, c.corner_min_eig = int(cfg.corner_win), float(cfg.corner_min_eig)
         h = ctypes.c_void_p()
         self.ctx.check(self.lib.me_vo_loop_create(self.ctx.h, self.tctx.h, ctypes.byref(c), ctypes.byref(h)),
                        "me_vo_loop_create")
