@@ -180,19 +180,38 @@ def test_ba_config3_bench_window(ctx, oracle):
     _ba_fixed(ctx, oracle, S.ba_problem(seed * 7 + 0, c["n_feats"], c["window"], c["width"], c["height"]), 10)
 
 
+@pytest.fixture
+def solve_flags(ctx):
+    """The test hook me_debug_solve_flags on the shared ctx: set_(word) must be
+    accepted; the word is 0 again after the test."""
+    import ctypes
+
+    hook = ctx.lib.me_debug_solve_flags
+    hook.argtypes = [ctypes.c_void_p, ctypes.c_int]
+
+    def set_(word):
+        assert hook(ctx.h, word) == 0
+
+    yield set_
+    set_(0)
+
+
+HOOK_ROSTER_NOW, HOOK_SEPARATE_ASM = 8192, 16384  # me_debug_solve_flags bits (csrc/me_internal.hpp)
+
+
 @pytest.mark.parametrize("cfg,iters", [(3, 10), (4, 4)])
-def test_ba_fused_assembly_identical(ctx, monkeypatch, cfg, iters):
+def test_ba_fused_assembly_identical(ctx, solve_flags, cfg, iters):
     """S assembly inside the camera-solve launch (default; LDS form at config 3,
-    global-memory form at config 4) vs its own s_assemble launch
-    (ME_BA_NOFUSEASM=1): the same sums in the same order, so bit-identical
-    cameras, points and summary."""
+    global-memory form at config 4) vs its own s_assemble launch (test hook
+    bit 16384): the same sums in the same order, so bit-identical cameras,
+    points and summary."""
     from uasl_motion_estimation_amd.optimisation import SolverOptions, ba_solve
 
     c = S.CONFIGS[cfg]
     bp = S.ba_problem(S.SEED0 + cfg, c["n_feats"], c["window"], c["width"], c["height"])
     out = {}
     for sep in ("0", "1"):
-        monkeypatch.setenv("ME_BA_NOFUSEASM", sep)
+        solve_flags(HOOK_SEPARATE_ASM if sep == "1" else 0)
         out[sep] = ba_solve(bp.copy(), SolverOptions.fixed_iterations(iters), ctx=ctx)
     (c0, p0, s0), (c1, p1, s1) = out["0"], out["1"]
     assert np.array_equal(c0, c1) and np.array_equal(p0, p1)
@@ -319,23 +338,14 @@ def test_klt_many_features_rare_weights(ctx, oracle):
 
 # ------------------------------------------------------------------ co-residency roster (csrc/roster.hpp)
 @pytest.fixture
-def roster_now(ctx):
+def roster_now(solve_flags):
     """Test hook me_debug_solve_flags(8192): every roster on this ctx closes at
     once, so the persistent scale LM and the camera solve's workers run on
     whichever workgroups had joined by then (usually a few: the rest leave
     at once and their units are dealt over the joined ones; with none, block
     0 works alone), and the camera solve's block 0 claims every fused
     assembly unit not yet claimed without waiting (roster.hpp CLAIM)."""
-    import ctypes
-
-    hook = ctx.lib.me_debug_solve_flags
-    hook.argtypes = [ctypes.c_void_p, ctypes.c_int]
-
-    def set_(on):
-        assert hook(ctx.h, 8192 if on else 0) == 0
-
-    yield set_
-    set_(False)
+    return lambda on: solve_flags(HOOK_ROSTER_NOW if on else 0)
 
 
 def test_roster_scale_lm_identical_at_any_participant_count(ctx, oracle, sp_cfg3, roster_now):
@@ -376,3 +386,35 @@ def test_roster_camera_solve_identical_at_any_participant_count(ctx, roster_now,
     assert np.array_equal(c0, c1) and np.array_equal(p0, p1)
     assert (s0["iterations"], s0["successful_steps"], s0["final_cost"]) == \
         (s1["iterations"], s1["successful_steps"], s1["final_cost"])
+
+
+def test_solve_flags_hook_refuses_every_other_bit(ctx, solve_flags):
+    """me_debug_solve_flags takes the test-hook bits only: the timing bits the
+    camera solve once read (1, 2, 4, 8, 256) and its internal image bit (4096)
+    are refused with ME_ERR_INVALID, alone or beside an accepted bit, and the
+    ctx's word stays as it was -- a 4-camera, 40-landmark solve gives the same
+    cameras and points bit for bit after each refusal.  An accepted word acts
+    (1024: every camera solve fails, the cameras stay put) and 0 clears it."""
+    from uasl_motion_estimation_amd.optimisation import SolverOptions, ba_solve
+
+    bp = S.ba_problem(S.SEED0, 40, 4, 640, 480)
+    assert len(bp.cams) == 4 and len(bp.pts) == 40
+
+    def solve():
+        return ba_solve(bp.copy(), SolverOptions.fixed_iterations(5), ctx=ctx)
+
+    c0, p0, s0 = solve()
+    assert s0["successful_steps"] > 0 and not np.array_equal(c0, bp.cams)
+    hook = ctx.lib.me_debug_solve_flags  # (argtypes: the solve_flags fixture)
+    for word in (1, 256, 4096, 8192 | 4):
+        assert hook(ctx.h, word) == -1, word  # ME_ERR_INVALID
+        assert b"me_debug_solve_flags" in ctx.lib.me_last_error(ctx.h)
+        c1, p1, _ = solve()
+        assert np.array_equal(c0, c1) and np.array_equal(p0, p1), word
+    solve_flags(1024 | 16384)
+    assert hook(ctx.h, 4096) == -1  # refused: the accepted word stays
+    c2, _, s2 = solve()
+    assert s2["successful_steps"] == 0 and np.array_equal(c2, bp.cams)
+    solve_flags(0)
+    c3, p3, _ = solve()
+    assert np.array_equal(c0, c3) and np.array_equal(p0, p3)

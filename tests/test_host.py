@@ -188,3 +188,76 @@ def test_scale_lm_launch_form_selection():
     assert "ME_SCALE_BLOCKS" not in src and "getenv(\"ME_SCALE" not in src
     assert "ME_SCALE_BLOCKS" not in open(os.path.join(ROOT, "bench.py")).read()
 
+
+def test_library_and_pipeline_read_no_environment_switch():
+    """The library reads no environment variable (timing experiments are -D
+    builds, test hooks go through me_debug_solve_flags), and the VO loops take
+    front_cus / async_enqueue / chain_window as arguments and attributes only."""
+    csrc = os.path.join(ROOT, "uasl_motion_estimation_amd", "csrc")
+    names = sorted(f for f in os.listdir(csrc) if os.path.isfile(os.path.join(csrc, f)))
+    assert "ba.hip" in names and "mi.hip" in names
+    for f in names:
+        assert "getenv(" not in open(os.path.join(csrc, f), errors="replace").read(), f
+    pipeline = open(os.path.join(ROOT, "uasl_motion_estimation_amd", "pipeline.py")).read()
+    for name in ("ME_VO_FRONT_CUS", "ME_VO_ASYNC_ENQUEUE", "ME_VO_CHAIN"):
+        assert name not in pipeline, name
+
+
+# (n_cams, fixed_frames, n_pts) -> spts, nsub, rsub, rlen, nruns, stpw, sgrp, ksplit, sorted, camera-solve form
+# (0 LDS, 1 global memory, 2 global memory with workers).  Tile pairs T (T + 1) / 2 of T = ceil((6 m + 1) / 16)
+# tiles for m variable cameras take the values 28, 36, 45, ... 78, 91, 105: the rule's thresholds at 40 and 100
+# pairs are pinned by their nearest reachable neighbours.
+_BA_GEOMETRY = {
+    (20, 2, 2000): (32, 63, 1, 32, 63, 16, 2, 128, 0, 0),    # config 3, 28 pairs: wide, two tile groups of 2 per wave
+    (30, 2, 8000): (32, 250, 1, 32, 250, 32, 3, 768, 1, 1),  # config 4, 66 pairs: sorted, 4 tiles per wave
+    (50, 2, 2000): (8, 250, 1, 8, 250, 40, 5, 1280, 1, 2),   # config 5, 190 pairs: 5 tiles per wave, workers
+    (20, 2, 4400): (32, 138, 1, 32, 138, 32, 1, 138, 0, 0),  # the config-3 VO window: wide, one tile group
+    (23, 2, 2000): (32, 63, 1, 32, 63, 16, 3, 192, 0, 1),    # 36 pairs (<= 40): split, unsorted
+    (24, 2, 2000): (32, 63, 1, 32, 63, 32, 2, 128, 1, 1),    # 45 pairs (> 40): 4 tiles per wave, sorted
+    (33, 2, 2000): (32, 63, 1, 32, 63, 32, 3, 192, 1, 1),    # 78 pairs: the last window whose 32-landmark Y block fits
+    (34, 2, 2000): (16, 125, 1, 16, 125, 32, 3, 384, 1, 1),  # 91 pairs: it does not, 16 landmarks
+    (36, 2, 2000): (16, 125, 1, 16, 125, 32, 3, 384, 1, 1),  # 91 pairs (<= 100): 16 landmarks, 4 tiles per wave
+    (37, 2, 2000): (8, 250, 1, 8, 250, 40, 3, 768, 1, 1),    # 105 pairs (> 100): 8 landmarks, 5 tiles per wave
+    (20, 2, 4096): (32, 128, 1, 32, 128, 16, 2, 256, 0, 0),  # np = 256 x kSchurPts: still split
+    (20, 2, 4097): (32, 129, 1, 32, 129, 32, 1, 129, 0, 0),  # one more: one tile group
+    (23, 2, 4096): (32, 128, 1, 32, 128, 16, 3, 384, 0, 1),
+    (23, 2, 4097): (32, 129, 1, 32, 129, 32, 2, 272, 0, 1),
+    (30, 2, 4096): (32, 128, 1, 32, 128, 32, 3, 384, 1, 1),  # beyond 40 pairs the landmark count changes the runs only
+    (30, 2, 4097): (32, 129, 1, 32, 129, 32, 3, 408, 1, 1),
+    (36, 2, 4096): (16, 256, 1, 16, 256, 32, 3, 768, 1, 1),  # 256 sub-chunks: one per run
+    (36, 2, 4097): (16, 257, 2, 32, 129, 32, 3, 408, 1, 1),  # 257: two per run
+    (20, 2, 8193): (32, 257, 2, 64, 129, 32, 1, 129, 0, 0),
+    (3, 2, 0): (32, 1, 1, 32, 1, 8, 1, 1, 0, 0),             # one variable camera, no landmark
+    (5, 2, 200): (32, 7, 1, 32, 7, 8, 1, 7, 0, 0),           # config 1
+    (10, 2, 500): (32, 16, 1, 32, 16, 16, 1, 16, 0, 0),      # config 2
+}
+
+
+def test_ba_schur_geometry_and_solve_form_selection():
+    """me_debug_ba_geometry (host only): the Schur pass's geometry and the
+    camera solve's launch form that a window takes, as the plan chooses them
+    (ba.hip schur_geometry, solve_form) -- the values the rule gave before it
+    was gathered into one function, at the benchmark configurations, the
+    config-3 VO window and both sides of each of its thresholds.  No
+    environment variable enters the choice."""
+    lib = _lib.load_library()
+    fn = lib.me_debug_ba_geometry
+    fn.argtypes = [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int)]
+    fn.restype = ctypes.c_int
+
+    def geometry(*window):
+        out = (ctypes.c_int * 10)()
+        assert fn(*window, out) == 0
+        return tuple(out)
+
+    for window, want in _BA_GEOMETRY.items():
+        assert geometry(*window) == want, window
+    switches = {"ME_SCHUR_PTS": "16", "ME_SCHUR_STPW": "40", "ME_SCHUR_SORT": "1", "ME_SOLVE_WORKERS": "3"}
+    os.environ.update(switches)  # ignored by the library
+    try:
+        assert geometry(20, 2, 2000) == _BA_GEOMETRY[(20, 2, 2000)]
+    finally:
+        for k in switches:
+            del os.environ[k]
+    assert fn(0, 0, 10, (ctypes.c_int * 10)()) == -1  # ME_ERR_INVALID
+

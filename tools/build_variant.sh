@@ -13,7 +13,7 @@ for f in $SRC; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -w "$@" -c $f -o $out/obj/${f%.hip}.o &
 done
 for f in $HOSTSRC; do
-  g++ -std=c++17 -O3 -fPIC -w -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include "$@" -c $f -o $out/obj/${f%.cpp}.o &
+  g++ -std=c++17 -O3 -fPIC -ffp-contract=off -w -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include "$@" -c $f -o $out/obj/${f%.cpp}.o &
 done
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $out/libme_hip.so $out/obj/*.o -L/opt/rocm/lib -Wl,-rpath,/opt/rocm/lib -lrccl -lrocprofiler-sdk-roctx

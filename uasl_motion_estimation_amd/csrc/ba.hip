@@ -1285,19 +1285,22 @@ __global__ __launch_bounds__(kBlock) void s_assemble_kernel(Geo g, Bufs b, Opts 
 #endif
 constexpr int kSolveBlock = ME_SOLVE_BLOCK;
 constexpr int kLoadBatch = 32;
-#define SOLVE_STAMP(i)                                                                      \
-  do {                                                                                      \
-    if ((skip & 256) && tid == 0) st->stamps[(i)] += (long long)__builtin_amdgcn_s_memtime(); \
-  } while (0)
-#define SOLVE_START(i)                                                                      \
-  do {                                                                                      \
-    if ((skip & 256) && tid == 0) st->stamps[(i)] -= (long long)__builtin_amdgcn_s_memtime(); \
-  } while (0)
 
 #ifdef ME_SOLVE_TS  // timing experiment only (tools/drivers.py solve_ts): wall-clock phases of cam_solve, 100 MHz ticks
 // [1] lin_finalize, [2] assembly wait, [3] load, [4] factorisation, [5] backward
 // solve, [6] candidate / cost tail, [8] last assembler exit - wg 0 entry,
 // [9] first assembler entry - wg 0 entry, [10] s_memtime ticks of [1..6], [15] calls
+// SOLVE_START / SOLVE_STAMP: s_memtime ticks of the phased loop's phases in
+// State::stamps (me_debug_read): [0] the barrier behind the load, [1] diagonal,
+// [2] panel, [3] trailing, [5] backward solve, [15] calls
+#define SOLVE_STAMP(i)                                                               \
+  do {                                                                               \
+    if (tid == 0) st->stamps[(i)] += (long long)__builtin_amdgcn_s_memtime();        \
+  } while (0)
+#define SOLVE_START(i)                                                               \
+  do {                                                                               \
+    if (tid == 0) st->stamps[(i)] -= (long long)__builtin_amdgcn_s_memtime();        \
+  } while (0)
 __device__ long long g_solve_ts[24];
 __device__ unsigned long long g_asm_first = ~0ull, g_asm_last = 0ull;
 #define STS_DECL long long sts_prev_ = 0, sts_t0_ = 0, sts_c0_ = 0
@@ -1336,6 +1339,8 @@ __device__ unsigned long long g_asm_first = ~0ull, g_asm_last = 0ull;
     }                                                                      \
   } while (0)
 #else
+#define SOLVE_STAMP(i) do {} while (0)
+#define SOLVE_START(i) do {} while (0)
 #define STS_DECL
 #define STS_BEGIN() do {} while (0)
 #define STS(k) do {} while (0)
@@ -1373,8 +1378,7 @@ constexpr unsigned kSolveTerm = 0x40000000u;  // epoch: stop (block 0 failed)
 // reads A only with sc1 loads after its barrier -- no release fence (an L2
 // write-back) and no acquire (an L1 invalidate) per hand-off.
 constexpr long kSolveSpin = 1L << 21;         // bounded waits (~0.5 s with s_sleep)
-constexpr int kSkipImg = 4096;                // cam_solve `skip` bit: [S + D; -b^T] already in Abuf (solver layout)
-constexpr int kSkipRosterNow = 8192;          // cam_solve `skip` bit (test hook): the roster closes at once
+// (cam_solve_kernel's `flags` bits: kFlag*, me_internal.hpp -- scale.hip and mi.hip read the ctx's word too)
 #ifndef ME_SOLVE_IMG
 #define ME_SOLVE_IMG 1  // non-fused assembly writes the solver's image (0: S | b | diag U, loaded by the solve)
 #endif
@@ -1646,7 +1650,7 @@ template <int kMode>
 // linearisation bookkeeping (lin_finalize) and, unless the solve has ended,
 // waits for the count (bounded), re-arms it and reads S with sc1 loads.  One
 // launch per LM iteration fewer than s_assemble_kernel + cam_solve_kernel.
-__global__ __launch_bounds__(kSolveBlock) void cam_solve_kernel(Geo g, Bufs b, Opts o, int skip, int nworkers, int nasm,
+__global__ __launch_bounds__(kSolveBlock) void cam_solve_kernel(Geo g, Bufs b, Opts o, int flags, int nworkers, int nasm,
                                                                 const double* gc_raw, unsigned asm_gen) {
   extern __shared__ double smem[];
   __shared__ double red[64];
@@ -1708,7 +1712,7 @@ __global__ __launch_bounds__(kSolveBlock) void cam_solve_kernel(Geo g, Bufs b, O
       s_steal = 0;
       if (live) {
         const long long t0 = (long long)__builtin_amdgcn_s_memrealtime();
-        const long long lim = (skip & kSkipRosterNow) ? 0 : me_roster::kCloseTicks;
+        const long long lim = (flags & kFlagRosterNow) ? 0 : me_roster::kCloseTicks;
         while (__hip_atomic_load(asm_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned)nasm) {
           if ((long long)__builtin_amdgcn_s_memrealtime() - t0 >= lim) {
             s_steal = 1;
@@ -1743,7 +1747,7 @@ __global__ __launch_bounds__(kSolveBlock) void cam_solve_kernel(Geo g, Bufs b, O
     }
     if (threadIdx.x == 0) {
       const int live = !st->done;
-      long k = (skip & 512) ? kSolveSpin : 0;  // (512: test hook, a forced timeout on this ctx)
+      long k = (flags & kFlagAsmTimeout) ? kSolveSpin : 0;  // (test hook: a forced timeout on this ctx)
       if (live && (s_steal || k)) {  // (all counted in the first wait: nothing left to wait for)
         for (; k < kSolveSpin; ++k) {
           if (__hip_atomic_load(asm_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) >= (unsigned)nasm) break;
@@ -1781,7 +1785,7 @@ __global__ __launch_bounds__(kSolveBlock) void cam_solve_kernel(Geo g, Bufs b, O
   // requested together: one round of global latency instead of a chain
   const int done = st->done;
   const int fail_in = st->fail || st->spin_err || (fused ? (b.xch && b.xch[xo_fail(g)] != 0.0) : b.scal[R_COUNT] != 0.0) ||
-                      (skip & 1024);  // (1024: test hook, a forced solve failure)
+                      (flags & kFlagSolveFail);  // (test hook: a forced solve failure)
   const double radius = st->radius;
   // [S + D; -b^T]: every load of a batch is issued from a computed index
   // before the first use, so a batch costs one round of global latency.
@@ -1798,7 +1802,7 @@ __global__ __launch_bounds__(kSolveBlock) void cam_solve_kernel(Geo g, Bufs b, O
   const int nn = n * n;
   // the image of [S + D; -b^T] in Abuf: written by s_assemble_kernel (non-fused), or by this launch's
   // assemblers (fused; written through)
-  const bool img_ready = (skip & kSkipImg) != 0 || (fused && (kLds || ME_SOLVE_IMG));
+  const bool img_ready = (flags & kFlagImg) != 0 || (fused && (kLds || ME_SOLVE_IMG));
   // LDS-DMA chunks of the image: all, or (pipelined form) the ones holding block row 0 first
   const int dma_bytes = N * ld * 8, dma_chunks = (dma_bytes + 1023) >> 10;
   const int dma_first = kPipe ? min(dma_chunks, (16 * ld * 8 + 1023) >> 10) : dma_chunks;
@@ -1878,9 +1882,11 @@ __global__ __launch_bounds__(kSolveBlock) void cam_solve_kernel(Geo g, Bufs b, O
     pdone = 0u;
     if (kMode == 2 && nworkers > 0)
       s_nwk = (int)me_roster::close<me_roster_dev>(b.roster, (unsigned)nworkers,
-                                                   fail_in || (skip & kSkipRosterNow) ? 0 : me_roster::kCloseTicks);
+                                                   fail_in || (flags & kFlagRosterNow) ? 0 : me_roster::kCloseTicks);
   }
-  if ((skip & 256) && tid == 0) st->stamps[15] += 1;
+#ifdef ME_SOLVE_TS
+  if (tid == 0) st->stamps[15] += 1;
+#endif
   SOLVE_START(0);
   __syncthreads();
   STS(3);
@@ -2064,9 +2070,9 @@ __global__ __launch_bounds__(kSolveBlock) void cam_solve_kernel(Geo g, Bufs b, O
         // waves 1-3 and 5-7 while wave 0 factors this block (wave 4 shares
         // wave 0's SIMD and stays out of its way)
         const bool sib = nw > 4 && wave == 4;  // wave 0's SIMD sibling
-        if (kLook && J > 0 && wave != 0 && !sib && !(skip & 4))
+        if (kLook && J > 0 && wave != 0 && !sib)
           trailing_split<kSc1>(A, ld, Ts, J - 1, false, wave - 1 - (nw > 4 && wave > 4), nw - 1 - (nw > 4), lane);
-        if (wave == 0 && !(skip & 1)) {
+        if (wave == 0) {
           const int q = lane >> 4;
           double4_t A4, Y4;
 #pragma unroll
@@ -2095,7 +2101,7 @@ __global__ __launch_bounds__(kSolveBlock) void cam_solve_kernel(Geo g, Bufs b, O
     // (b) panel on the matrix cores: L_IJ = A_IJ X_J^T
     {
       const double* XJ = X + 256 * J;
-      for (int I = J + 1 + wave; I < ((skip & 2) ? 0 : Ts); I += nw) {
+      for (int I = J + 1 + wave; I < Ts; I += nw) {
         const int i0 = 16 * I;
         double av[4], bv[4];
 #pragma unroll
@@ -2115,12 +2121,10 @@ __global__ __launch_bounds__(kSolveBlock) void cam_solve_kernel(Geo g, Bufs b, O
     SOLVE_START(3);
     // (c) trailing update on the matrix cores: A_IK -= L_IJ L_KJ^T, J < K <= I
     {
-      if (!(skip & 4)) {
-        if (kLook)
-          trailing_split<kSc1>(A, ld, Ts, J, true, wave, nw, lane);  // column J + 1 now, the rest with the next block
-        else
-          trailing_tiles<kSc1>(A, ld, Ts, J, wave, nw, lane);
-      }
+      if (kLook)
+        trailing_split<kSc1>(A, ld, Ts, J, true, wave, nw, lane);  // column J + 1 now, the rest with the next block
+      else
+        trailing_tiles<kSc1>(A, ld, Ts, J, wave, nw, lane);
       __syncthreads();
     }
     SOLVE_STAMP(3);
@@ -2145,7 +2149,7 @@ __global__ __launch_bounds__(kSolveBlock) void cam_solve_kernel(Geo g, Bufs b, O
   // workgroup barrier on the chain: a wave waits only for the blocks of other
   // waves, and the lanes' L entries of the next block are requested one block
   // ahead (global forms: a memory round trip per block otherwise).
-  const int Jlast = (skip & 8) ? -1 : (n - 1) >> 4;
+  const int Jlast = (n - 1) >> 4;
   // Global forms only: in the LDS form the two-barrier loop below is faster
   // (config 3: 3.7 vs 5.3 us); at W = 50 this one is (17.4 vs 19.9 us).
   if (!kLds && N <= nt) {
@@ -3188,20 +3192,91 @@ struct Plan {
   size_t solve_lds = 0;
   size_t schur_lds = 0;
   int use_lds = 0;
-  int diag_skip = 0;  // ME_SOLVE_SKIP: timing diagnostics only (results invalid)
+  int solve_flags = 0;  // cam_solve_kernel `flags`: the ctx's test-hook bits the kernel reads (kFlag*)
   int n_enq = 0;      // linearisations queued so far (the first runs the camera assembly on its own)
-  bool sequential = false;  // ME_BA_SEQUENTIAL=1: never fuse (A/B timing)
-  bool no_fused_asm = false;  // ME_BA_NOFUSEASM=1: S assembly in its own launch (A/B timing)
+  bool no_fused_asm = false;  // test hook kFlagSeparateAsm: S assembly in its own launch
   bool full_S = false;      // assemble both block triangles of S (reduced-system / covariance read-back)
-  int solve_workers = -1;   // global-memory camera solve: trailing-update workgroups (-1: by size; ME_SOLVE_WORKERS)
   int solve_cap = 0;        // co-resident cam_solve_kernel<2> workgroups on the ctx's CUs (0: not queried)
-  int warned_workers = 0;   // an explicit worker count was clamped (reported once per plan)
   me_comm* comm = nullptr;  // sharded solve: the exchange (null: one GPU)
   bool xmax_separate = false;  // ABI-v2 callback (no rank): the gradient max-norm travels in its own max all-reduce
 };
 
 inline long rup(long x, long m) { return (x + m - 1) / m * m; }
 int blocks(long n, int bs) { return (int)std::max(1L, (n + bs - 1) / bs); }
+
+// Geometry of the Schur pass (pt_schur_kernel) from the tile pairs, the
+// landmarks and the padded row length; me_debug_ba_geometry and
+// tests/test_host.py pin what it chooses.  The landmarks are cut into
+// sub-chunks of spts, rsub sub-chunks make a run (at most ~256 runs), and a
+// run's tiles are dealt to sgrp tile groups of stpw = 8 waves x NT <= 5 tiles;
+// the grid is runs, in blocks of 8 (one per XCD) when a run has several
+// groups, x sgrp (surplus groups and padding runs exit at once).
+//  * spts: 32 whenever the Y block of 32 landmarks fits the LDS (Rpad <= 192):
+//    half the partial tiles for the assembly to sum (config 4: -2% BA time;
+//    the config-3 VO window of ~4 400 landmarks, where 16-landmark sub-chunks
+//    outnumber 256 workgroups: BA_SCHUR 430 -> 340 us per keyframe).  Else 16,
+//    or 8 beyond 100 pairs: the contraction is MFMA-bound per workgroup and
+//    twice the workgroups spread it over more CUs (config 5: BA 5.2 -> 4.96 ms
+//    per 10 iterations; config 3 is slower with 8).
+//  * NT: 4 tiles per wave up to 100 pairs (config 4: 5 spill), 5 beyond (the
+//    50-keyframe window: fewer tile groups per run recompute fewer Y blocks).
+//    Few tiles and landmarks (at most 40 pairs and 256 x 16 landmarks; config
+//    3: 28 pairs, 2 000 landmarks) take 2, so a 32-landmark run is split into
+//    two tile groups: the same 48 MFMAs per wave as 16 landmarks x 4 tiles at
+//    half the runs, the run's Y block formed twice (pt_schur 15.8 -> 14.9 us,
+//    cam_solve 31.8 -> 31.4 us per iteration; undivided 32-landmark runs were
+//    slower there than 16-landmark ones, 1.23 vs 1.19 ms per 10 iterations:
+//    the longer per-workgroup chain).
+//  * sorted: the runs in band order (plan_band / plan_order) beyond 40 pairs
+//    (config 4: 66, config 5: 190); at config 3 the two plan launches cost
+//    more than the partial traffic saves.
+void schur_geometry(int npairs, int np, int Rpad, Geo& g) {
+  const bool wide = schur_lds_bytes(kSchurPtsWide, Rpad) <= kSchurLdsCap;
+  const bool split_wide = wide && npairs <= 40 && np <= 256 * kSchurPts;
+  g.spts = wide ? kSchurPtsWide : npairs > 100 ? kSchurPtsSmall : kSchurPts;
+  g.nsub = (int)std::max(1L, ((long)np + g.spts - 1) / g.spts);
+  g.rsub = (int)std::max(1L, ((long)g.nsub + 255) / 256);
+  g.rlen = g.spts * g.rsub;
+  g.nruns = (int)std::max(1L, ((long)np + g.rlen - 1) / g.rlen);
+  const int nt = split_wide ? 2 : npairs > 100 ? kSchurNtMax : std::min(kSchurNtMax, 4);
+  g.stpw = 8 * std::min((npairs + 7) / 8, nt);
+  g.sgrp = (npairs + g.stpw - 1) / g.stpw;
+  g.ksplit = (g.sgrp > 1 ? (int)rup((long)g.nruns, 8) : g.nruns) * g.sgrp;
+  g.sorted = npairs > 40 ? 1 : 0;
+}
+
+// The sizes that follow from the window alone: the camera system and the Schur pass's geometry.
+void ba_geometry(Geo& g, int n_cams, int fixed_frames, int n_pts) {
+  g.nc = n_cams;
+  g.np = n_pts;
+  g.nf = std::min(std::max(fixed_frames, 0), n_cams);
+  g.m = g.nc - g.nf;
+  g.n6 = 6 * g.m;
+  g.Rpad = (int)rup(g.n6 + 1, 16);  // camera columns | z_p column n6 | zero padding
+  g.T = g.Rpad / 16;
+  g.Ts = (g.n6 + 1 + 15) / 16;
+  g.npairs = g.T * (g.T + 1) / 2;
+  schur_geometry(g.npairs, g.np, g.Rpad, g);
+}
+
+// camera-solve launch form by size alone: 0 = LDS, 1 = global memory, 2 = with workers
+// (enqueue_iteration: 2 runs as 1 where the ctx's CUs can host no worker beside block 0)
+constexpr size_t kSolveLdsCap = 150 * 1024;
+inline int solve_form(int Ts) {
+  if (8 * (solve_small_doubles(Ts) + solve_a_doubles(Ts)) <= kSolveLdsCap) return 0;
+  return Ts >= kSolveMwMinTs ? 2 : 1;
+}
+
+// Host-only debug symbol (tests/test_host.py pins it; not part of the ABI).
+// out[10]: spts, nsub, rsub, rlen, nruns, stpw, sgrp, ksplit, sorted, camera-solve form
+extern "C" int me_debug_ba_geometry(int n_cams, int fixed_frames, int n_pts, int* out) {
+  if (n_cams <= 0 || n_pts < 0 || !out) return ME_ERR_INVALID;
+  Geo g;
+  ba_geometry(g, n_cams, fixed_frames, n_pts);
+  const int v[10] = {g.spts, g.nsub, g.rsub, g.rlen, g.nruns, g.stpw, g.sgrp, g.ksplit, g.sorted, solve_form(g.Ts)};
+  std::memcpy(out, v, sizeof v);
+  return ME_OK;
+}
 
 int ba_drain(me_ctx* c);
 
@@ -3227,82 +3302,20 @@ int plan_build(me_ctx* c, const me_ba_problem* p, const me_ba_options* opt, Plan
     }
   }
   P.c = c;
-  if (const char* sk = getenv("ME_SOLVE_SKIP")) P.diag_skip = atoi(sk);
-  int dbg = c->dbg_solve_flags;
-  if (dbg & 2048) {  // (test hook: every second solve on this ctx has every camera solve fail)
-    if (c->dbg_solve_count++ & 1) dbg |= 1024;
-    dbg &= ~2048;
-  }
-  P.diag_skip |= dbg;
-  if (const char* sw = getenv("ME_SOLVE_WORKERS")) P.solve_workers = atoi(sw);  // A/B timing (0: one workgroup)
-  if (const char* sq = getenv("ME_BA_SEQUENTIAL")) P.sequential = atoi(sq) != 0;
-  if (const char* fa = getenv("ME_BA_NOFUSEASM")) P.no_fused_asm = atoi(fa) != 0;
+  // the ctx's test-hook word (me_debug_solve_flags): the host-only bits are translated here
+  int hook = c->dbg_solve_flags;
+  if ((hook & kFlagFailEveryOther) && (c->dbg_solve_count++ & 1)) hook |= kFlagSolveFail;
+  P.no_fused_asm = (hook & kFlagSeparateAsm) != 0;
+  P.solve_flags = hook & (kFlagAsmTimeout | kFlagSolveFail | kFlagRosterNow);
   Geo& g = P.g;
-  g.nc = p->n_cams;
-  g.np = p->n_pts;
+  ba_geometry(g, p->n_cams, p->fixed_frames, p->n_pts);
   g.no = p->n_obs;
-  g.nf = std::min(std::max(p->fixed_frames, 0), p->n_cams);
   g.od = mono ? 2 : 4;
   // sharded: one gradient max-norm slot per rank (ABI-v2 callback without rank: one slot, max-reduced apart)
   P.comm = comm;
   P.xmax_separate = comm && comm->world == 0;
   g.xslots = comm && comm->world > 0 ? comm->world : 1;
   g.xrank = comm && comm->world > 0 ? comm->rank : 0;
-  g.m = g.nc - g.nf;
-  g.n6 = 6 * g.m;
-  g.Rpad = (int)rup(g.n6 + 1, 16);  // camera columns | z_p column n6 | zero padding
-  g.T = g.Rpad / 16;
-  g.Ts = (g.n6 + 1 + 15) / 16;
-  g.npairs = g.T * (g.T + 1) / 2;
-  // wide sub-chunks pay off once the tile count is large (config 4: 66 pairs,
-  // -2% BA time); at config 3 (28 pairs) the longer per-workgroup chain costs
-  // more than the halved partial traffic saves (1.23 vs 1.19 ms per 10 iterations)
-  // landmarks per Schur sub-chunk: 32 while the Y block fits the LDS (half the
-  // partial tiles for s_assemble); else 16, or 8 for many tiles (the
-  // contraction is MFMA-bound per workgroup: twice the workgroups spread it
-  // over more CUs; config 5: BA 5.2 -> 4.96 ms per 10 iterations, config 3
-  // slower with 8)
-  // (and once 16-landmark sub-chunks outnumber 256 workgroups: the config-3
-  // VO window, ~4 400 landmarks, BA_SCHUR 430 -> 340 us per keyframe)
-  // Few tiles and landmarks (config 3: 28 pairs, 2 000 landmarks): 32-landmark
-  // sub-chunks whose run is split into two tile groups of 2 tiles per wave --
-  // the same 48 MFMAs per wave as 16 landmarks x 4 tiles, half the runs, so
-  // half the partial tiles written here and summed by the assembly
-  // (pt_schur 15.8 -> 14.9 us, cam_solve 31.8 -> 31.4 us per iteration,
-  // rocprofv3 A/B); a run's Y block is formed twice (once per group).
-  const bool split_wide = g.npairs <= 40 && g.np <= 256 * kSchurPts &&
-                          schur_lds_bytes(kSchurPtsWide, g.Rpad) <= kSchurLdsCap;
-  if ((g.npairs > 40 || g.np > 256 * kSchurPts || split_wide) && schur_lds_bytes(kSchurPtsWide, g.Rpad) <= kSchurLdsCap)
-    g.spts = kSchurPtsWide;
-  else
-    g.spts = g.npairs > 100 ? kSchurPtsSmall : kSchurPts;
-  if (const char* e = getenv("ME_SCHUR_PTS")) {  // A/B timing only
-    const int v = atoi(e);
-    if (v == kSchurPts || v == kSchurPtsSmall || (v == kSchurPtsWide && schur_lds_bytes(kSchurPtsWide, g.Rpad) <= kSchurLdsCap))
-      g.spts = v;
-  }
-  g.nsub = (int)std::max(1L, ((long)g.np + g.spts - 1) / g.spts);
-  // Schur runs: rsub sub-chunks of spts landmarks each (at most ~256 runs), in
-  // band order; each run split into tile groups of 8 waves x NT <= 5 tiles
-  g.rsub = (int)std::max(1L, ((long)g.nsub + 255) / 256);
-  g.rlen = g.spts * g.rsub;
-  g.nruns = (int)std::max(1L, ((long)g.np + g.rlen - 1) / g.rlen);
-  // (measured, tools/drivers.py ba_wall: 4 tiles per wave at config 4 -- 5 spill -- but 5 for
-  // the 50-keyframe window, where fewer tile groups per run recompute fewer Y blocks)
-  g.stpw = 8 * std::min((g.npairs + 7) / 8, g.npairs > 100 ? kSchurNtMax : std::min(kSchurNtMax, 4));
-  if (split_wide && g.spts == kSchurPtsWide) g.stpw = std::min(g.stpw, 16);
-  if (const char* e = getenv("ME_SCHUR_STPW")) {  // A/B timing only: tiles per group (8 x tiles per wave)
-    const int v = atoi(e);
-    if (v >= 16 && v <= 8 * kSchurNtMax && v % 8 == 0) g.stpw = v;
-  }
-  g.sgrp = (g.npairs + g.stpw - 1) / g.stpw;
-  // Schur workgroups: runs in blocks of 8 (one per XCD) x sgrp tile groups (a
-  // run's surplus tile groups and the padding runs exit at once)
-  g.ksplit = (g.sgrp > 1 ? (int)rup((long)g.nruns, 8) : g.nruns) * g.sgrp;
-  // band order pays once the tile set is large (config 4: 66 pairs, config 5: 190); for
-  // config 3 (28 pairs) the two plan launches cost more than the partial traffic saves
-  g.sorted = g.npairs > 40 ? 1 : 0;
-  if (const char* e = getenv("ME_SCHUR_SORT")) g.sorted = atoi(e) != 0;  // A/B timing only
   ME_CHECK(c, g.nruns <= kMaxRuns, "BA: %d Schur runs exceed %d", g.nruns, kMaxRuns);
   g.nblkp = blocks(std::max(g.np, 1), kBlock);
   ME_CHECK(c, g.npairs <= 8 * 24, "BA: %d variable cameras exceed the Schur tile budget", g.m);
@@ -3472,10 +3485,9 @@ int plan_build(me_ctx* c, const me_ba_problem* p, const me_ba_options* opt, Plan
   }
   ME_TRY(me_check_launch(c, "BA plan"));
   // LDS for the camera solve
-  P.solve_lds = 8 * (solve_small_doubles(g.Ts) + solve_a_doubles(g.Ts));
-  P.use_lds = P.solve_lds <= 150 * 1024 ? 1 : 0;
-  if (!P.use_lds) P.solve_lds = 8 * solve_small_doubles(g.Ts);
-  ME_CHECK(c, P.solve_lds <= 150 * 1024, "BA: %d variable cameras exceed the camera-solve workspace", g.m);
+  P.use_lds = solve_form(g.Ts) == 0 ? 1 : 0;
+  P.solve_lds = 8 * (solve_small_doubles(g.Ts) + (P.use_lds ? solve_a_doubles(g.Ts) : 0));
+  ME_CHECK(c, P.solve_lds <= kSolveLdsCap, "BA: %d variable cameras exceed the camera-solve workspace", g.m);
   P.schur_lds = schur_lds_bytes(g.spts, g.Rpad);
   ME_CHECK(c, P.schur_lds <= kSchurLdsCap, "BA: %d variable cameras exceed the Schur workspace", g.m);
   // dynamic-LDS ceilings of the solve and Schur kernels: set once per context
@@ -3483,7 +3495,7 @@ int plan_build(me_ctx* c, const me_ba_problem* p, const me_ba_options* opt, Plan
   // host time in front of every queued solve)
   if (!c->ba_lds_attr) {
     for (const void* k : {(const void*)cam_solve_kernel<0>, (const void*)cam_solve_kernel<1>, (const void*)cam_solve_kernel<2>})
-      ME_HIP(c, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
+      ME_HIP(c, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSolveLdsCap));
 #define ME_SCHUR_K(N)                                                                                   \
   (const void*)pt_schur_kernel<N, 512, kSchurPts>, (const void*)pt_schur_kernel<N, 512, kSchurPtsWide>, \
       (const void*)pt_schur_kernel<N, 512, kSchurPtsSmall>
@@ -3495,13 +3507,12 @@ int plan_build(me_ctx* c, const me_ba_problem* p, const me_ba_options* opt, Plan
   // the multi-workgroup camera solve deals its tiles over the workers that
   // joined its roster (roster.hpp), so residency is never assumed; the
   // workers launched are still capped by what fits on the ctx's CUs (more
-  // could only join late and leave), and an explicit worker count is clamped
-  // by it too
+  // could only join late and leave)
   if (!P.use_lds) {
     int per_cu = 0;
     ME_HIP(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, cam_solve_kernel<2>, kSolveBlock, P.solve_lds));
     P.solve_cap = std::max(0, per_cu) * (c->cu_active > 0 ? c->cu_active : c->num_cu);
-    if (P.comm && (g.Ts >= kSolveMwMinTs || P.solve_workers > 0)) {
+    if (P.comm && g.Ts >= kSolveMwMinTs) {
       // Sharded: every rank solves the camera system redundantly and must run
       // the same solve form (worker count) on the same operands, whatever its
       // own CU mask: the smallest capacity over the ranks (one max exchange of
@@ -3549,7 +3560,7 @@ int enqueue_linearize(Plan& P) {
   // blocks are then scaled by the fixed global scaling, and the exchange sums
   // them.
   const bool first = P.n_enq == 0;
-  const bool fused = !first && g.m > 0 && !P.sequential;
+  const bool fused = !first && g.m > 0;
   ++P.n_enq;
   CamArgs ca{P.cpart, P.colnorm, P.gc_raw, P.Uraw, fused ? 1 : 0, fused ? (g.m * g.ck + 7) / 8 * 8 : 0};
   if (g.m > 0 && !fused)
@@ -3645,24 +3656,14 @@ int enqueue_iteration(Plan& P, bool last = false) {
   // solve; config 4 (11 steps) is faster on one workgroup (118 vs 131 us: the
   // per-step hand-offs).  The workers are capped by what can be co-resident.
   const int np0 = (g.Ts - 1) * g.Ts / 2;
-  int nwk = P.use_lds ? 0
-            : P.solve_workers >= 0 ? P.solve_workers
-            : g.Ts >= kSolveMwMinTs ? std::min(64, std::max(1, (np0 + kSolveBlock / 64 - 1) / (kSolveBlock / 64)))
-                                    : 0;
-  if (nwk > 0) {
-    const int cap = std::max(0, std::min(nwk, P.solve_cap - 1));
-    if (P.solve_workers > 0 && cap != nwk && !P.warned_workers) {  // an explicit count the CUs cannot host
-      std::fprintf(stderr, "me_ba: ME_SOLVE_WORKERS=%d exceeds the co-resident capacity, using %d\n", nwk, cap);
-      P.warned_workers = 1;
-    }
-    nwk = cap;
-  }
+  int nwk = solve_form(g.Ts) == 2 ? std::min(64, std::max(1, (np0 + kSolveBlock / 64 - 1) / (kSolveBlock / 64))) : 0;
+  nwk = std::max(0, std::min(nwk, P.solve_cap - 1));
   // S = U - sum of the Schur partials is assembled by wide workgroups
   // (coalesced, all CUs) rather than by the one-workgroup solve, whose
   // dependent cross-XCD loads would otherwise dominate the iteration.  Modes
   // 0 and 1 they ride in the camera-solve launch (fused assembly; sharded:
   // they unpack the exchanged system).
-  const bool fuse = g.m > 0 && !P.full_S && !last && !P.sequential && nwk == 0 && !P.no_fused_asm;
+  const bool fuse = g.m > 0 && !P.full_S && !last && nwk == 0 && !P.no_fused_asm;
   const int nasm = fuse ? blocks((long)g.npairs * 256, kSolveBlock / kSaGroups) : 0;
   const bool img = !fuse && !last && g.m > 0 && !P.full_S && ME_SOLVE_IMG;
   if (!fuse) ME_TRY(enqueue_assemble(P, img));
@@ -3671,7 +3672,7 @@ int enqueue_iteration(Plan& P, bool last = false) {
   {
     me_ktimer t(c, ME_KT_BA_SOLVE);
     const double* gc = P.gc_raw;
-    const int sk = P.diag_skip | (img ? kSkipImg : 0);
+    const int sk = P.solve_flags | (img ? kFlagImg : 0);
     const unsigned gen = nasm > 0 ? ++P.asm_gen : 0u;  // fused assembly: this launch's claim generation
     if (P.use_lds)
       hipLaunchKernelGGL(cam_solve_kernel<0>, dim3(1 + nasm), dim3(kSolveBlock), P.solve_lds, s, g, P.b, P.o, sk, 0,
@@ -4381,15 +4382,25 @@ extern "C" int me_ba_window_indices(me_ctx* c, const int32_t* frame, const int32
   return me_check_launch(c, "window_indices_kernel");
 }
 
-// Test hook (not part of the drop-in ABI): flags OR-ed into this ctx's camera
-// solve diagnostics; 512 forces the fused-assembly wait to time out
-// (tests/test_distributed.py: a hand-off timeout on one rank of a sharded solve),
-// 1024 fails every camera solve (each LM step invalid: the solve ends with
-// termination 2 after max_num_consecutive_invalid_steps), 2048 does that to
-// every second solve queued on the ctx (tests/test_pipeline.py: the chained
-// window start after a failed BA).
+// The test hook (not part of the drop-in ABI): the ctx's hook word, any
+// combination of the kHookMask bits (me_internal.hpp); 0 clears it.  Any other
+// bit is refused and leaves the word as it was.
+//    512 kFlagAsmTimeout      the fused-assembly wait of the camera solve times out
+//                             (tests/test_distributed.py: a hand-off timeout on one rank of a sharded solve)
+//   1024 kFlagSolveFail       every camera solve fails: each LM step invalid, the solve ends with
+//                             termination 2 after max_num_consecutive_invalid_steps
+//   2048 kFlagFailEveryOther  that, for every second solve queued on the ctx
+//                             (tests/test_pipeline.py: the chained window start after a failed BA)
+//   8192 kFlagRosterNow       every roster on the ctx closes at once: the scale LM, the camera solve's
+//                             workers and fused assemblers (tests/test_gpu_configs.py roster tests)
+//  16384 kFlagSeparateAsm     S assembly in its own launch, not inside the camera solve's
+//                             (tests/test_gpu_configs.py test_ba_fused_assembly_identical)
+//  32768 kFlagMiLane          the one-lane-per-pair MI kernel instead of the quad kernel
+//                             (tests/test_gpu_parity.py test_mi_lane_kernel_still_bit_exact)
 extern "C" int me_debug_solve_flags(me_ctx* c, int flags) {
   if (!c) return ME_ERR_INVALID;
+  ME_CHECK(c, (flags & ~kHookMask) == 0, "me_debug_solve_flags: 0x%x holds bits that are no test hook (accepted: 0x%x)",
+           (unsigned)flags, (unsigned)kHookMask);
   c->dbg_solve_flags = flags;
   c->dbg_solve_count = 0;
   return ME_OK;

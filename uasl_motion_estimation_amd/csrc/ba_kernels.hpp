@@ -63,7 +63,7 @@ struct State {
   double x_cost, cand_cost, model_change, initial_cost;
   double cam_step2, cam_xn2, cam_model;  // cam_model: -(g_c.y_c + y_c^T U y_c / 2), this rank's camera part
   double last_q;
-  long long stamps[16];  // s_memtime at cam_solve phase ends (ME_SOLVE_SKIP & 256)
+  long long stamps[16];  // timing builds only (-DME_SOLVE_TS, -DME_SCHUR_STAMPS): s_memtime phase stamps, me_debug_read
 };
 
 // Scalars reduced from block partials (one slot per quantity).

@@ -13,6 +13,21 @@ struct me_timer_pair {
   int kernel;
 };
 
+// The flag word of the camera solve (cam_solve_kernel `flags`) and of the
+// ctx's test hook (me_debug_solve_flags, ba.hip: what each hook bit is for).
+// The library reads no environment variable: timing experiments are -D builds
+// (tools/build_variant.sh), test hooks are the kHookMask bits of this word.
+enum : int {
+  kFlagAsmTimeout = 512,    // hook: the fused-assembly wait times out
+  kFlagSolveFail = 1024,    // hook: every camera solve fails
+  kFlagFailEveryOther = 2048,  // hook, host only: kFlagSolveFail for every second solve queued on the ctx
+  kFlagImg = 4096,          // internal: [S + D; -b^T] already in Abuf (solver layout)
+  kFlagRosterNow = 8192,    // hook: every roster closes at once
+  kFlagSeparateAsm = 16384,  // hook, host only: S assembly in its own launch
+  kFlagMiLane = 32768,      // hook, host only: the one-lane-per-pair MI kernel
+  kHookMask = kFlagAsmTimeout | kFlagSolveFail | kFlagFailEveryOther | kFlagRosterNow | kFlagSeparateAsm | kFlagMiLane,
+};
+
 struct me_ctx {
   int device = 0;
   int num_cu = 256;  // compute units of the device (grid sizing of streaming kernels)
@@ -40,7 +55,7 @@ struct me_ctx {
   int rand_f = 3, rand_r = 0;
   bool rand_init = false;
   long long dbg[16] = {0};  // diagnostics (last BA solve phase stamps)
-  int dbg_solve_flags = 0;        // test hook (me_debug_solve_flags): OR-ed into the camera solve's diagnostic flags
+  int dbg_solve_flags = 0;       // test-hook word (me_debug_solve_flags: kHookMask bits only)
   unsigned dbg_solve_count = 0;  // solves queued since the hook was set (reset by it)
   // asynchronous BA solve in flight (me_ba_solve_async / me_ba_wait, ba.hip):
   // its own pinned staging, so later calls on the ctx cannot overwrite it

@@ -12,7 +12,6 @@
 //  * terms use the glibc log2f restatement (me_device.hpp): bit-exact floats.
 #include "me_internal.hpp"
 #include "me_device.hpp"
-#include <cstring>
 
 using namespace me_dev;
 
@@ -806,14 +805,8 @@ __global__ __launch_bounds__(kLargeBlock) void entropy_kernel(const uint8_t* __r
 
 inline float inv_count(long n) { return (float)(1.0 / (double)n); }
 
-// ME_MI_KERNEL=lane selects the one-lane-per-pair kernel (A/B timing; same results)
-inline bool mi_use_lane_kernel() {
-  static const bool lane = [] {
-    const char* e = getenv("ME_MI_KERNEL");
-    return e && strcmp(e, "lane") == 0;
-  }();
-  return lane;
-}
+// test hook (me_debug_solve_flags): the one-lane-per-pair kernel (same results)
+inline bool mi_use_lane_kernel(const me_ctx* c) { return (c->dbg_solve_flags & kFlagMiLane) != 0; }
 
 // Epipolar MI stereo matcher of the VO loop (pipeline.WindowedStereoVO.
 // stereo_match / _pick, restated on the device).  Two passes:
@@ -937,7 +930,7 @@ static int epipolar_launch(me_ctx* c, const uint8_t* imgL, const uint8_t* imgR, 
     // one lane per candidate pair (table-driven terms, the batch kernel's bits)
     EpiMap em{uv, lo, valid, status, n_dev, nd, d_max, width, height, patch / 2, margin, (double*)sc};
     const long img_bytes = (long)stride * (height - 1) + width;
-    if (!mi_use_lane_kernel()) {
+    if (!mi_use_lane_kernel(c)) {
       const int qb = (int)std::min<long>((pairs + kQuadGroups - 1) / kQuadGroups, 16384);
       hipLaunchKernelGGL((mi_quad_kernel<11, 11, true>), dim3(qb), dim3(kQuadBlock), 0, c->stream, imgL, stride, imgR,
                          stride, img_bytes, img_bytes, nullptr, nullptr, n, 11, 11, tab, (int)(4 * mi_tab_size(121)),
@@ -1012,7 +1005,7 @@ int me_launch_mi_pairs(me_ctx* c, const uint8_t* dL, int sL, const uint8_t* dR, 
   ME_TRY(me_mi_table(c, npx, &tab));
   // bounds of the realigned 16-byte row loads: never read past the images
   const long img_bytes_L = (long)sL * (height - 1) + width, img_bytes_R = (long)sR * (height - 1) + width;
-  if (!mi_use_lane_kernel()) {
+  if (!mi_use_lane_kernel(c)) {
     const int qb = (int)std::min<long>(((long)n + kQuadGroups - 1) / kQuadGroups, 16384);
     const int tb = (int)(4 * mi_tab_size(npx));
     if (pw == 11 && ph == 11)

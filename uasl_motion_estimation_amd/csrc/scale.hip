@@ -1623,7 +1623,7 @@ extern "C" int me_scale_optimise(me_ctx* c, me_scale_state* s, const me_optim_pa
     lp.mirror_done_only = 1;
     // (test hook 8192: the roster closes at once, so the phases run on the
     // workgroups that joined by then -- the same results from fewer of them)
-    lp.roster_ticks = (c->dbg_solve_flags & 8192) ? 0 : me_roster::kCloseTicks;
+    lp.roster_ticks = (c->dbg_solve_flags & kFlagRosterNow) ? 0 : me_roster::kCloseTicks;
     {
       me_ktimer t(c, ME_KT_SCALE_RES);
       const int max_phases = 256 * (p.max_nb_iter + 2);

@@ -69,14 +69,16 @@ class Worker {
     cv_.notify_all();
     return queued_;
   }
-  int wait(long seq) {
+  // seq < 0: every job queued so far (queued_ is read under the lock)
+  int wait(long seq = -1) {
     std::unique_lock<std::mutex> lk(m_);
+    if (seq < 0) seq = queued_;
     cv_.wait(lk, [&] { return done_ >= seq; });
     const int r = rc_;
     rc_ = ME_OK;
     return r;
   }
-  int wait_all() { return wait(queued_); }
+  int wait_all() { return wait(); }
 
  private:
   void run() {

@@ -352,7 +352,6 @@ class GPUBackend(Backend):
         # persistent scale-LM kernel needs its workgroups co-resident, which
         # the BA's kernels on shared CUs would not leave room for
         self._masked = False
-        front_cus = int(os.environ.get("ME_VO_FRONT_CUS", front_cus))  # A/B timing
         if self.tctx is not self.ctx and 0 < front_cus < 16:
             import torch
 
@@ -371,7 +370,7 @@ class GPUBackend(Backend):
         # one call at a time (me_hip.h), so neither the scale LM nor the BA
         # queueing runs on a worker thread -- both run inline, in loop order
         self.shared_ctx = self.tctx is self.ctx
-        self.async_enqueue = os.environ.get("ME_VO_ASYNC_ENQUEUE", "1") == "1" and not self.shared_ctx
+        self.async_enqueue = not self.shared_ctx
         self._imgs = {}
         # device-resident BA window: obs (4 doubles) | frame | track ID per
         # observation, frame by frame; [_wstart, _wend) live in store _wcur
@@ -387,7 +386,7 @@ class GPUBackend(Backend):
         self._baq = []  # queued BA solves, oldest first (at most two: window t chained behind t - 1)
         self._bw_k = 0  # staging / device buffer set of the next window solve
         # window t's BA start formed on the device behind window t - 1's solve (me_vo_ba_chain)
-        self.chain_window = os.environ.get("ME_VO_CHAIN", "1") == "1"
+        self.chain_window = True
         self.tlog = None  # diagnostics: (event, frame, perf_counter) of BA enqueues / completions
         self._scale_res = None
 
@@ -1478,7 +1477,6 @@ class NativeStereoVO:
         self._own_t = tctx is None and overlap
         self.tctx = tctx or (Context(self.ctx.device) if overlap else self.ctx)
         self._masked = False
-        front_cus = int(os.environ.get("ME_VO_FRONT_CUS", front_cus))
         if self.tctx is not self.ctx and 0 < front_cus < 16:
             import torch
 
