@@ -779,6 +779,30 @@ inline void calcOpticalFlowPyrLK(const amd::ImageView& prev, const amd::ImageVie
             "calcOpticalFlowPyrLK");
 }
 
+// The same with the forward-backward check (A12c, me_klt_track_fb): tracked
+// prev -> next, then back from the result; status[i] = 1 only if both passes
+// tracked the feature and it returned within fb_max (> 0, pixels) of pts_in[i].
+// fb_err[i] = that distance, +inf where a pass failed; pts_out is the forward
+// pass's output for every feature.
+inline void calcOpticalFlowPyrLK(const amd::ImageView& prev, const amd::ImageView& next,
+                                 const std::vector<Point2f>& pts_in, std::vector<Point2f>& pts_out,
+                                 std::vector<uint8_t>& status, std::vector<float>& fb_err, double fb_max,
+                                 amd::Context& ctx = amd::Context::thread_default()) {
+  if (prev.rows != next.rows || prev.cols != next.cols || prev.step != next.step)
+    throw std::invalid_argument("calcOpticalFlowPyrLK: images differ in shape");
+  if (!(fb_max > 0.0)) throw std::invalid_argument("calcOpticalFlowPyrLK: fb_max must be > 0");
+  pts_out.resize(pts_in.size());
+  status.assign(pts_in.size(), 0);
+  fb_err.assign(pts_in.size(), 0.f);
+  if (pts_in.empty()) return;
+  me_klt_params kp;
+  me_klt_default_params(&kp);
+  ctx.check(me_klt_track_fb(ctx.get(), ME_HOST, prev.data, next.data, prev.cols, prev.rows, prev.step,
+                            &pts_in[0].x, &pts_out[0].x, status.data(), fb_err.data(), (int)pts_in.size(), &kp,
+                            fb_max),
+            "calcOpticalFlowPyrLK");
+}
+
 // Corner response of an 8-bit image (A12b, no reference counterpart: the
 // application's feature detector): rows x cols doubles, the KLT's minimum
 // eigenvalue of the win x win window centred on each pixel, 0 where the KLT

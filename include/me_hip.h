@@ -411,6 +411,7 @@ typedef struct {
   int detector;               /* new features of a keyframe: 0 grid (me_vo_new_cells), 1 corners (me_vo_new_corners) */
   int corner_win;             /* me_corner_params of the corner detector (21, 1e-4) */
   double corner_min_eig;
+  double klt_fb_max;          /* > 0: the tracker is me_klt_track_fb with this bound (pixels); 0: me_klt_track */
 } me_vo_loop_config;
 typedef struct {              /* pipeline.FrameResult */
   int t, n_tracked, n_new, n_active, n_window_pts, n_window_obs;
@@ -557,6 +558,30 @@ typedef struct { int win; int max_level; int max_iters; double eps; double min_e
 void me_klt_default_params(me_klt_params* p);
 int me_klt_track(me_ctx* ctx, me_mem mem, const uint8_t* prev, const uint8_t* next, int width, int height,
                  int stride, const float* pts_in, float* pts_out, uint8_t* status, int n, const me_klt_params* p);
+
+/* ---- A12c: forward-backward KLT check (build-defined; no reference) -----
+ * me_klt_track prev -> next, then back next -> prev from where it arrived;
+ * a feature is kept only if it returns to where it started.  With the same
+ * me_klt_params for both passes:
+ *  1. (q, sf) = me_klt_track(prev, next, pts_in); pts_out = q, bit for bit,
+ *     for every feature (those with sf = 0 included).
+ *  2. (r, sb) = me_klt_track(next, prev, q): the template and its Scharr
+ *     derivatives come from the next pyramid at every level, the search runs
+ *     in the prev pyramid and starts at q (no initial guess).
+ *  3. dx = (double)r.x - (double)pts_in.x, dy likewise; d2 = dx * dx + dy * dy
+ *     in FP64, in this order, no contraction.
+ *  4. status = 1 iff sf == 1 && sb == 1 && d2 <= fb_max * fb_max, else 0.
+ *  5. fb_err = (float)sqrt(d2) (correctly rounded FP64 sqrt, round-to-nearest
+ *     cast) when sf == 1 && sb == 1, else +inf.  fb_err may be NULL.
+ * The backward pass of a feature with sf = 0 is skipped.  Arguments are those
+ * of me_klt_track plus fb_max > 0 (NaN, 0 and negative values are rejected;
+ * +inf accepts every feature both passes tracked); n = 0 is allowed; ME_HOST /
+ * ME_DEVICE as in me_klt_track (asynchronous on the ctx stream in device
+ * mode).  The definition is restated in numpy around any tracker in
+ * pipeline.klt_fb_host (the checker, with oracle/klt.cpp as the tracker). */
+int me_klt_track_fb(me_ctx* ctx, me_mem mem, const uint8_t* prev, const uint8_t* next, int width, int height,
+                    int stride, const float* pts_in, float* pts_out, uint8_t* status, float* fb_err /* n, may be NULL */,
+                    int n, const me_klt_params* p, double fb_max);
 
 /* ---- A12b: corner detector (build-defined; no reference) ---------------
  * Where the VO loop starts new tracks: the pixels that maximise the quantity

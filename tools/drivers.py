@@ -15,6 +15,9 @@ loads another build of libme_hip.so (tools/build_variant.sh).
   corners [--reps --loop N]
                          corner detector kernels (1280x720, 3840x2160) and the config-3 native loop with
                          detector 0 / 1, alternating
+  klt_fb [--reps --repeats --check --loop N]
+                         me_klt_track_fb beside me_klt_track on the config-3 frame (2000 features), alternating
+                         in one process, and the config-3 native loop with klt_fb_max 0 / 0.5, alternating
 """
 import argparse
 import ctypes
@@ -434,6 +437,122 @@ def cmd_corners(a):
     print(json.dumps(out))
 
 
+def cmd_klt_fb(a):
+    """The forward-backward check (csrc/klt.hip, me_klt_track_fb) beside the
+    plain tracker on cmd_klt's inputs: per call, the ME_KT_PYR events (pyramids
+    and Scharr derivatives; the check adds the next pyramid's derivatives) and
+    the ME_KT_KLT events (plain: klt_kernel; check: forward pass, backward
+    pass and gate under one event pair), --repeats blocks of --reps calls
+    each, the two entry points alternating.  Then (--loop N) the native VO
+    loop at config 3 over N corridor keyframes with klt_fb_max 0 and 0.5,
+    alternating, two repeats each."""
+    import torch
+
+    from uasl_motion_estimation_amd import pipeline as PL
+    from uasl_motion_estimation_amd import synthetic as S
+    from uasl_motion_estimation_amd._lib import ME_DEVICE
+    from uasl_motion_estimation_amd.klt import klt_params
+    ctx = _setup(a.lib)
+    V = ctypes.c_void_p
+    W, H, N = 1280, 720, 2000
+    scene, K, stream = S.stereo_stream(20261018, W, H, 2)
+    pts = S.grid_features(np.random.default_rng(0), N, W, H, 12).astype(np.float32)
+    dp, dn, din, dout, dst, derr = (ctx.malloc(W * H), ctx.malloc(W * H), ctx.malloc(8 * N), ctx.malloc(8 * N),
+                                    ctx.malloc(N), ctx.malloc(4 * N))
+    L0, L1 = np.ascontiguousarray(stream[0].left), np.ascontiguousarray(stream[1].left)
+    ctx.h2d(dp, L0)
+    ctx.h2d(dn, L1)
+    ctx.h2d(din, pts)
+    kp = klt_params()
+
+    def plain():
+        ctx.check(ctx.lib.me_klt_track(ctx.h, ME_DEVICE, V(dp), V(dn), W, H, W, V(din), V(dout), V(dst), N,
+                                       ctypes.byref(kp)), "me_klt_track")
+
+    def fb():
+        ctx.check(ctx.lib.me_klt_track_fb(ctx.h, ME_DEVICE, V(dp), V(dn), W, H, W, V(din), V(dout), V(dst), V(derr), N,
+                                          ctypes.byref(kp), a.fb_max), "me_klt_track_fb")
+    out = {"inputs": f"{W}x{H}, {N} features, fb_max {a.fb_max}", "reps": a.reps, "calls": []}
+    for fn in (plain, fb):
+        for _ in range(5):
+            fn()
+    ctx.synchronize()
+    for rep in range(a.repeats):
+        for name, fn in (("me_klt_track", plain), ("me_klt_track_fb", fb)):
+            ctx.timing_reset()
+            ctx.timing(True, ["KLT", "PYR"])
+            w0 = time.perf_counter()
+            for _ in range(a.reps):
+                fn()
+            ctx.synchronize()
+            wall = (time.perf_counter() - w0) / a.reps * 1e6
+            ctx.timing(False)
+            r = {"call": name, "repeat": rep, "wall_us_per_call": round(wall, 2)}
+            for fam in ("PYR", "KLT"):
+                cnt, ms = ctx.timing_read(fam)
+                r[f"{fam}_us_per_call"] = round(1000 * ms / max(cnt, 1), 2)
+                r[f"{fam}_timed"] = cnt
+            out["calls"].append(r)
+            print(json.dumps(r), flush=True)
+    got, gst, gerr = np.zeros((N, 2), np.float32), np.zeros(N, np.uint8), np.zeros(N, np.float32)
+    ctx.d2h(got, dout)
+    ctx.d2h(gst, dst)
+    ctx.d2h(gerr, derr)
+    out["accepted"] = int(gst.sum())
+    out["both_passes_tracked"] = int(np.isfinite(gerr).sum())
+    if a.check:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import oracle as O  # checker only
+        fwd, fst = O.klt(L0, L1, pts)
+        q, st, err = PL.klt_fb_host(O.klt, L0, L1, pts, a.fb_max)
+        same = (np.array_equal(got.view(np.uint32), q.view(np.uint32)) and np.array_equal(gst, st)
+                and np.array_equal(gerr.view(np.uint32), err.view(np.uint32)))
+        out["forward_tracked"] = int(fst.sum())
+        print(f"klt_fb parity vs oracle: {'bit-exact' if same else 'MISMATCH'} (forward {int(fst.sum())}, both passes "
+              f"{out['both_passes_tracked']}, accepted {out['accepted']} of {N})", flush=True)
+        if not same:
+            sys.exit(1)
+    for d in (dp, dn, din, dout, dst, derr):
+        ctx.free(d)
+    if a.loop > 0:
+        c, NK = 3, a.loop
+        arc = S.trajectory_arc(max(NK, 2))
+        truth = [np.concatenate([t, S.R_to_aa_robust(R)]) for (R, t) in arc]
+        K = S.intrinsics(1280, 720)
+        frames = []
+        for c0 in range(0, NK, 50):
+            _, fr = S.corridor_frames_torch(S.SEED0 + c, 1280, 720, c0, min(50, NK - c0))
+            frames += [(Lk.contiguous(), Rk.contiguous()) for (Lk, Rk, _, _) in fr]
+            torch.cuda.synchronize()
+            print(f"rendered {len(frames)} keyframes", flush=True)
+        runs = []
+        for rep in range(-1, 2):  # (-1: a short untimed run, the first loop of a process pays the allocations)
+            for fb_max in (0.0, a.fb_max):
+                cfg = PL.PipelineConfig.from_config(c, klt_fb_max=fb_max)
+                vo = PL.NativeStereoVO(cfg, ctx, K, truth[0], truth[1] - truth[0], log_events=False, overlap=True)
+                t0 = time.perf_counter()
+                for t in range(NK if rep >= 0 else min(NK, 30)):
+                    vo.process(t, *frames[t])
+                vo.finish()
+                dt = time.perf_counter() - t0
+                if rep < 0:
+                    vo.close()
+                    continue
+                st = vo._stats()
+                res = vo.results
+                vo.close()
+                names = ["klt_match", "first_match", "scale_submit", "window_submit", "ba_result", "scale_result"]
+                r = {"klt_fb_max": fb_max, "repeat": rep, "keyframes": NK, "keyframes_per_s": round(NK / dt, 2),
+                     "tracked_mean": round(float(np.mean([q.n_tracked for q in res[2:]])), 1),
+                     "new_mean": round(float(np.mean([q.n_new for q in res[2:]])), 1),
+                     "host_s": round(st[0], 4), "blocked_s": round(st[1], 4),
+                     "wait_ms_per_keyframe": {k: round(1e3 * st[3 + i] / NK, 4) for i, k in enumerate(names)}}
+                runs.append(r)
+                print(json.dumps(r), flush=True)
+        out["loop_config3"] = runs
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--lib", default=os.environ.get("ME_LIB"))
@@ -461,6 +580,12 @@ def main():
     p.add_argument("configs", nargs="?", default="3,4")
     p = sub.add_parser("corners")
     p.add_argument("--reps", type=int, default=200)
+    p.add_argument("--loop", type=int, default=200, help="keyframes of the config-3 native loop per run (0: skip)")
+    p = sub.add_parser("klt_fb")
+    p.add_argument("--reps", type=int, default=200)
+    p.add_argument("--repeats", type=int, default=3)
+    p.add_argument("--fb-max", dest="fb_max", type=float, default=0.5)
+    p.add_argument("--check", type=int, default=1)
     p.add_argument("--loop", type=int, default=200, help="keyframes of the config-3 native loop per run (0: skip)")
     a = ap.parse_args()
     globals()["cmd_" + a.cmd](a)

@@ -126,7 +126,8 @@ class VOLoopConfigC(ctypes.Structure):
                 ("scale_iters", c_int), ("fixed_frames", c_int), ("d_min", c_int), ("d_max", c_int),
                 ("baseline", c_double), ("feat_var", c_double), ("K", c_double * 9), ("first_pose", c_double * 6),
                 ("velocity", c_double * 6), ("has_velocity", c_int), ("log_events", c_int),
-                ("async_enqueue", c_int), ("detector", c_int), ("corner_win", c_int), ("corner_min_eig", c_double)]
+                ("async_enqueue", c_int), ("detector", c_int), ("corner_win", c_int), ("corner_min_eig", c_double),
+                ("klt_fb_max", c_double)]
 
 
 class VOFrameResultC(ctypes.Structure):
@@ -166,7 +167,7 @@ EXPORTS = [
     "me_vo_ba_chain", "me_vo_window_submit",
     "me_comm_unique_id", "me_comm_create_rccl", "me_comm_create_callback", "me_comm_destroy", "me_comm_info",
     "me_comm_allreduce", "me_comm_calibrate", "me_comm_exchange_us", "me_ba_shard_worthwhile_comm", "me_ba_solve_comm", "me_ba_shard_worthwhile", "me_ba_shard_exchange_us",
-    "me_klt_default_params", "me_klt_track",
+    "me_klt_default_params", "me_klt_track", "me_klt_track_fb",
     "me_corner_default_params", "me_corner_response", "me_vo_new_corners",
     "me_nms_scanline3x3",
     "me_vo_default_params", "me_vo_srand", "me_vo_rand", "me_vo_process",
@@ -308,6 +309,8 @@ def load_library(path: str | None = None):
         "me_klt_default_params": (None, [P(KLTParamsC)]),
         "me_klt_track": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                  c_void_p, c_int, P(KLTParamsC)]),
+        "me_klt_track_fb": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                    c_void_p, c_void_p, c_int, P(KLTParamsC), c_double]),
         "me_corner_default_params": (None, [P(CornerParamsC)]),
         "me_corner_response": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, P(CornerParamsC), c_void_p]),
         "me_vo_new_corners": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,

@@ -13,6 +13,9 @@
 //  * the 2x2 solve runs redundantly in every lane; the window position, its
 //    bilinear weights and the region tests are wave-uniform and kept in
 //    scalar registers (the weight packing runs on the scalar unit).
+// me_klt_track_fb (me_hip.h A12c) is the forward-backward check on the same
+// kernels: derivatives of the next pyramid too, a second klt_kernel launch on
+// the pyramid view with the two images swapped, and a per-feature gate.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -220,14 +223,32 @@ __device__ __forceinline__ void stage_region(uint32_t* reg, const uint8_t* __res
 // Every lane loads all of its window pixels unconditionally (pixels past the
 // window alias pixel 0 and are masked afterwards), so the loads of one step
 // issue back to back behind a single wait instead of one round trip per pixel.
+//
+// kGated (the backward pass of me_klt_track_fb): a feature whose gate byte is
+// 0, or whose start lies outside the level-0 image (the tracker then reports
+// status 0 whatever it computes), is not tracked: status 0, pout = pin.  The
+// test is wave-uniform and the plain instance compiles without it.
+template <bool kGated>
 __global__ __launch_bounds__(256) void klt_kernel(Pyr P, const float* __restrict__ pin, float* __restrict__ pout,
                                                   uint8_t* __restrict__ status, int n, int win, int max_iters,
-                                                  double eps2, double min_eig) {
+                                                  double eps2, double min_eig, const uint8_t* __restrict__ gate) {
   __shared__ __attribute__((aligned(16))) uint32_t regions[4][kRegion * kRegion];
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (scalar: the feature, its region and
   const int f = blockIdx.x * 4 + wv;                                 // its window origin live in scalar registers)
   if (f >= n) return;  // wave-uniform
+  if constexpr (kGated) {
+    const float gx = pin[2 * f], gy = pin[2 * f + 1];
+    const bool inside = gx >= 0.f && gx < (float)P.w[0] && gy >= 0.f && gy < (float)P.h[0];  // (false for NaN)
+    if (!gate[f] || !inside) {
+      if (lane == 0) {
+        pout[2 * f] = gx;
+        pout[2 * f + 1] = gy;
+        status[f] = 0;
+      }
+      return;
+    }
+  }
   uint32_t* reg = regions[wv];
   const int half = (win - 1) / 2, npx = win * win;
   const double FLT_SCALE = 1.0 / (1 << 20);
@@ -438,9 +459,13 @@ extern "C" void me_klt_default_params(me_klt_params* p) {
   p->min_eig = 1e-4;
 }
 
-// Builds the pyramids of prev (with derivatives) and next into scratch.
+
+// Builds the pyramids of prev (with derivatives) and next into scratch.  With
+// B given (me_klt_track_fb) the next levels get derivatives too, stored behind
+// the plain layout, and B is the view with the two images swapped: template
+// and derivatives from next, search in prev.
 static int build_pyramids(me_ctx* c, const uint8_t* dprev, const uint8_t* dnext, int w, int h, int stride, int nl,
-                          Pyr& P) {
+                          Pyr& P, Pyr* B = nullptr) {
   std::vector<int> W(nl), H(nl);
   W[0] = w;
   H[0] = h;
@@ -450,6 +475,8 @@ static int build_pyramids(me_ctx* c, const uint8_t* dprev, const uint8_t* dnext,
   }
   size_t bytes = 0;
   for (int l = 0; l < nl; ++l) bytes += 2 * (size_t)W[l] * H[l] + 4 * (size_t)W[l] * H[l] + 64;
+  if (B)
+    for (int l = 0; l < nl; ++l) bytes += 4 * (size_t)W[l] * H[l] + 6 * 64;  // (and the plain layout's rounding)
   void* base;
   ME_TRY(me_scratch(c, SLOT_KLT_PYR, bytes + 1024, &base));
   char* p = (char*)base;
@@ -474,6 +501,18 @@ static int build_pyramids(me_ctx* c, const uint8_t* dprev, const uint8_t* dnext,
     P.dy[l] = (int16_t*)p;
     p += (2 * npx + 63) / 64 * 64;
   }
+  if (B) {
+    *B = P;
+    for (int l = 0; l < nl; ++l) {
+      size_t npx = (size_t)W[l] * H[l];
+      B->I[l] = P.J[l];
+      B->J[l] = P.I[l];
+      B->dx[l] = (int16_t*)p;
+      p += (2 * npx + 63) / 64 * 64;
+      B->dy[l] = (int16_t*)p;
+      p += (2 * npx + 63) / 64 * 64;
+    }
+  }
   hipStream_t s = c->stream;
   me_ktimer t(c, ME_KT_PYR);
   for (int l = 1; l < nl; ++l) {  // both images per launch
@@ -484,54 +523,123 @@ static int build_pyramids(me_ctx* c, const uint8_t* dprev, const uint8_t* dnext,
   {  // derivatives of every prev level in one launch
     dim3 blk(32, 8), grd((W[0] + 31) / 32, (H[0] + 7) / 8, nl);
     hipLaunchKernelGGL(scharr_levels_kernel, grd, blk, 0, s, P);
+    if (B) hipLaunchKernelGGL(scharr_levels_kernel, grd, blk, 0, s, *B);  // and of every next level
   }
   return me_check_launch(c, "pyramid kernels");
 }
 
-extern "C" int me_klt_track(me_ctx* c, me_mem mem, const uint8_t* prev, const uint8_t* next, int w, int h,
-                            int stride, const float* pin, float* pout, uint8_t* status, int n,
-                            const me_klt_params* kp) {
-  me_range range_("me_klt_track");
+namespace {
+
+// The forward-backward gate (me_hip.h A12c steps 3-5), one thread per feature:
+// r = the backward pass's result, sf / sb the two passes' status bytes.  The
+// FP64 operations are spelled out so that none is contracted into an fma.
+__global__ void klt_fb_gate_kernel(const float* __restrict__ pin, const float* __restrict__ r,
+                                   const uint8_t* __restrict__ sf, const uint8_t* __restrict__ sb,
+                                   uint8_t* __restrict__ status, float* __restrict__ fb_err, int n, double fb_max2) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const bool both = sf[i] == 1 && sb[i] == 1;
+  const double dx = __dsub_rn((double)r[2 * i], (double)pin[2 * i]);
+  const double dy = __dsub_rn((double)r[2 * i + 1], (double)pin[2 * i + 1]);
+  const double d2 = __dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy));
+  status[i] = both && d2 <= fb_max2 ? 1 : 0;
+  if (fb_err) fb_err[i] = both ? (float)__dsqrt_rn(d2) : __builtin_inff();
+}
+
+// me_klt_track (fb = false) and me_klt_track_fb: argument checks, staging of
+// host-mode arguments, pyramids, kernels.
+int klt_run(me_ctx* c, const char* who, me_mem mem, const uint8_t* prev, const uint8_t* next, int w, int h, int stride,
+            const float* pin, float* pout, uint8_t* status, float* fb_err, int n, const me_klt_params* kp, bool fb,
+            double fb_max) {
   if (!c || !kp) return ME_ERR_INVALID;
-  ME_CHECK(c, w > 0 && h > 0 && stride >= w && n >= 0, "me_klt_track: bad image");
+  ME_CHECK(c, w > 0 && h > 0 && stride >= w && n >= 0, "%s: bad image", who);
   ME_CHECK(c, kp->win >= 3 && (kp->win & 1) && kp->win * kp->win <= 64 * kMaxWinPx,
-           "me_klt_track: window must be odd and <= 21");
-  ME_CHECK(c, kp->max_level >= 0 && kp->max_level < kMaxLevels, "me_klt_track: max_level out of range");
+           "%s: window must be odd and <= 21", who);
+  ME_CHECK(c, kp->max_level >= 0 && kp->max_level < kMaxLevels, "%s: max_level out of range", who);
+  if (fb) ME_CHECK(c, fb_max > 0.0, "%s: fb_max must be > 0 (got %g)", who, fb_max);  // (false for NaN)
   ME_HIP(c, hipSetDevice(c->device));
   const int nl = kp->max_level + 1;
+  const size_t m = (size_t)std::max(n, 1);
   const uint8_t *dprev = prev, *dnext = next;
   const float* dpin = pin;
   float* dpout = pout;
   uint8_t* dst = status;
+  float* derr = fb_err;
+  // fb: the backward result and the two passes' status bytes
+  float* dback = nullptr;
+  uint8_t *dsf = nullptr, *dsb = nullptr;
   if (mem == ME_HOST) {
     void *a, *b, *pts;
     size_t bytes = (size_t)stride * (h - 1) + w;
     ME_TRY(me_scratch(c, SLOT_IMG_L, bytes, &a));
     ME_TRY(me_scratch(c, SLOT_IMG_R, bytes, &b));
-    ME_TRY(me_scratch(c, SLOT_KLT_PTS, 17 * (size_t)std::max(n, 1) + 64, &pts));
+    // pin 8 | pout 8 | status 1 per feature; fb: | backward 8 | fb_err 4 | sf 1 | sb 1
+    ME_TRY(me_scratch(c, SLOT_KLT_PTS, (fb ? 31 : 17) * m + 64, &pts));
     ME_HIP(c, hipMemcpyAsync(a, prev, bytes, hipMemcpyHostToDevice, c->stream));
     ME_HIP(c, hipMemcpyAsync(b, next, bytes, hipMemcpyHostToDevice, c->stream));
     dprev = (const uint8_t*)a;
     dnext = (const uint8_t*)b;
     dpin = (const float*)pts;
-    dpout = (float*)pts + 2 * (size_t)std::max(n, 1);
-    dst = (uint8_t*)((float*)pts + 4 * (size_t)std::max(n, 1));
+    dpout = (float*)pts + 2 * m;
+    dst = (uint8_t*)((float*)pts + 4 * m);
+    if (fb) {
+      dback = (float*)pts + 4 * m;
+      float* e = (float*)pts + 6 * m;
+      if (fb_err) derr = e;
+      dst = (uint8_t*)(e + m);
+      dsf = dst + m;
+      dsb = dsf + m;
+    }
     if (n) ME_HIP(c, hipMemcpyAsync((void*)dpin, pin, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+  } else if (fb) {
+    void* pts;
+    ME_TRY(me_scratch(c, SLOT_KLT_PTS, 10 * m + 64, &pts));
+    dback = (float*)pts;
+    dsf = (uint8_t*)(dback + 2 * m);
+    dsb = dsf + m;
   }
-  Pyr P;
-  ME_TRY(build_pyramids(c, dprev, dnext, w, h, stride, nl, P));
+  Pyr P, B;
+  ME_TRY(build_pyramids(c, dprev, dnext, w, h, stride, nl, P, fb ? &B : nullptr));
   if (n > 0) {
     me_ktimer t(c, ME_KT_KLT);
-    hipLaunchKernelGGL(klt_kernel, dim3((n + 3) / 4), dim3(256), 0, c->stream, P, dpin, dpout, dst, n, kp->win,
-                       kp->max_iters, kp->eps * kp->eps, kp->min_eig);
+    const dim3 grd((n + 3) / 4), blk(256);
+    const double eps2 = kp->eps * kp->eps;
+    if (!fb) {
+      hipLaunchKernelGGL(klt_kernel<false>, grd, blk, 0, c->stream, P, dpin, dpout, dst, n, kp->win, kp->max_iters,
+                         eps2, kp->min_eig, (const uint8_t*)nullptr);
+    } else {
+      hipLaunchKernelGGL(klt_kernel<false>, grd, blk, 0, c->stream, P, dpin, dpout, dsf, n, kp->win, kp->max_iters,
+                         eps2, kp->min_eig, (const uint8_t*)nullptr);
+      hipLaunchKernelGGL(klt_kernel<true>, grd, blk, 0, c->stream, B, (const float*)dpout, dback, dsb, n, kp->win,
+                         kp->max_iters, eps2, kp->min_eig, (const uint8_t*)dsf);
+      hipLaunchKernelGGL(klt_fb_gate_kernel, dim3((n + 255) / 256), blk, 0, c->stream, dpin, (const float*)dback,
+                         (const uint8_t*)dsf, (const uint8_t*)dsb, dst, derr, n, fb_max * fb_max);
+    }
   }
   ME_TRY(me_check_launch(c, "klt_kernel"));
   if (mem == ME_HOST) {
     if (n) {
       ME_HIP(c, hipMemcpyAsync(pout, dpout, 8 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
       ME_HIP(c, hipMemcpyAsync(status, dst, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+      if (fb && fb_err) ME_HIP(c, hipMemcpyAsync(fb_err, derr, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     }
     ME_HIP(c, hipStreamSynchronize(c->stream));
   }
   return ME_OK;
+}
+
+}  // namespace
+
+extern "C" int me_klt_track(me_ctx* c, me_mem mem, const uint8_t* prev, const uint8_t* next, int w, int h,
+                            int stride, const float* pin, float* pout, uint8_t* status, int n,
+                            const me_klt_params* kp) {
+  me_range range_("me_klt_track");
+  return klt_run(c, "me_klt_track", mem, prev, next, w, h, stride, pin, pout, status, nullptr, n, kp, false, 0.0);
+}
+
+extern "C" int me_klt_track_fb(me_ctx* c, me_mem mem, const uint8_t* prev, const uint8_t* next, int w, int h,
+                               int stride, const float* pin, float* pout, uint8_t* status, float* fb_err, int n,
+                               const me_klt_params* kp, double fb_max) {
+  me_range range_("me_klt_track_fb");
+  return klt_run(c, "me_klt_track_fb", mem, prev, next, w, h, stride, pin, pout, status, fb_err, n, kp, true, fb_max);
 }

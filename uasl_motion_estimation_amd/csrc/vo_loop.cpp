@@ -519,9 +519,14 @@ struct me_vo_loop {
     VL_TRY(me_memcpy_async(tctx, d_in, hp, 8 * (size_t)n), "klt H2D");
     me_klt_params kp;
     me_klt_default_params(&kp);
-    VL_TRY(me_klt_track(tctx, ME_DEVICE, prev.L, cur.L, cfg.width, cfg.height, cfg.width, (const float*)d_in,
-                        (float*)dres, (uint8_t*)dres + 12 * (size_t)n, n, &kp),
-           "me_klt_track");
+    if (cfg.klt_fb_max > 0.0)  // the forward-backward check: its combined status is the byte the matcher gates on
+      VL_TRY(me_klt_track_fb(tctx, ME_DEVICE, prev.L, cur.L, cfg.width, cfg.height, cfg.width, (const float*)d_in,
+                             (float*)dres, (uint8_t*)dres + 12 * (size_t)n, nullptr, n, &kp, cfg.klt_fb_max),
+             "me_klt_track_fb");
+    else
+      VL_TRY(me_klt_track(tctx, ME_DEVICE, prev.L, cur.L, cfg.width, cfg.height, cfg.width, (const float*)d_in,
+                          (float*)dres, (uint8_t*)dres + 12 * (size_t)n, n, &kp),
+             "me_klt_track");
     return ME_OK;
   }
   // GPUBackend.klt_match_new: tracked features' matcher, the cells they leave
@@ -1281,6 +1286,7 @@ void me_vo_loop_default_config(me_vo_loop_config* c) {
   c->detector = 0;
   c->corner_win = 21;
   c->corner_min_eig = 1e-4;
+  c->klt_fb_max = 0.0;
 }
 
 int me_vo_loop_create(me_ctx* ba, me_ctx* front, const me_vo_loop_config* cfg, me_vo_loop** out) {
@@ -1296,6 +1302,9 @@ int me_vo_loop_create(me_ctx* ba, me_ctx* front, const me_vo_loop_config* cfg, m
       (cfg->corner_win < 3 || cfg->corner_win > 31 || !(cfg->corner_win & 1) || !(cfg->corner_min_eig > 0.0)))
     return me_set_error(ba, ME_ERR_INVALID,
                         "me_vo_loop_create: corner_win must be odd and in [3, 31], corner_min_eig > 0");
+  if (!(cfg->klt_fb_max >= 0.0))  // (false for NaN)
+    return me_set_error(ba, ME_ERR_INVALID,
+                        "me_vo_loop_create: klt_fb_max must be >= 0 (0: no forward-backward check)");
   auto v = std::make_unique<me_vo_loop>();
   v->ctx = ba;
   v->tctx = front;

@@ -124,10 +124,13 @@ class PipelineConfig:
     detector: str = "grid"        # new features of a keyframe: "grid" (new_cells) or "corners" (corners.py)
     corner_win: int = 21
     corner_min_eig: float = 1e-4
+    klt_fb_max: float = 0.0       # > 0: forward-backward check of the tracker, bound in pixels (klt_fb_host); 0: off
 
     def __post_init__(self):
         if self.detector not in DETECTORS:
             raise ValueError(f"detector must be one of {DETECTORS}")
+        if not self.klt_fb_max >= 0.0:  # (false for NaN)
+            raise ValueError("klt_fb_max must be >= 0 (0: no forward-backward check)")
 
     @staticmethod
     def from_config(c: int, **kw) -> "PipelineConfig":
@@ -205,6 +208,28 @@ def _pick(uv, d, sc, nd, unique, ratio):
     return xr_f, ok
 
 
+def klt_fb_host(klt, prev, cur, pts, fb_max: float):
+    """Forward-backward check around any tracker klt(prev, cur, pts) ->
+    (pts_out, status): the numpy restatement of me_klt_track_fb
+    (include/me_hip.h A12c), FP64 in the order given there.  Returns (pts_out
+    of the forward pass, combined status, fb_err float32: the round-trip
+    distance, inf where a pass failed)."""
+    if not fb_max > 0.0:
+        raise ValueError("fb_max must be > 0")
+    pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
+    q, sf = klt(prev, cur, pts)
+    q = np.ascontiguousarray(q, np.float32).reshape(-1, 2)
+    r, sb = klt(cur, prev, q)
+    both = (np.asarray(sf) == 1) & (np.asarray(sb) == 1)
+    with np.errstate(invalid="ignore", over="ignore"):  # (features a pass lost: any value, masked below)
+        dx = np.asarray(r, np.float32)[:, 0].astype(np.float64) - pts[:, 0].astype(np.float64)
+        dy = np.asarray(r, np.float32)[:, 1].astype(np.float64) - pts[:, 1].astype(np.float64)
+        d2 = dx * dx + dy * dy
+        status = (both & (d2 <= np.float64(fb_max) * np.float64(fb_max))).astype(np.uint8)
+        fb_err = np.where(both, np.sqrt(d2), np.inf).astype(np.float32)
+    return q, status, fb_err
+
+
 def new_cells(t: int, uv_good: np.ndarray, grid) -> np.ndarray:
     """New features of keyframe t: the good tracked features (uv_good) occupy
     their grid cell (trunc((u - MARGIN) / cw), trunc((v - MARGIN) / ch)),
@@ -244,6 +269,7 @@ class Backend:
 
     d_max = 128
     detector = ("grid", 21, 1e-4)  # (detector, corner_win, corner_min_eig) of the loop's configuration
+    klt_fb_max = 0.0  # PipelineConfig.klt_fb_max of the loop's configuration (0: no forward-backward check)
 
     def frame_images(self, t: int, left: np.ndarray, right: np.ndarray):
         raise NotImplementedError
@@ -286,7 +312,10 @@ class Backend:
         """KLT of the submitted points, then the MI search (lo, nd, dvalid per
         point) of those that pass the KLT gate: (uv, status, xr, ok)."""
         prev, cur, pts = h
-        uv, st = self.klt(prev, cur, pts)
+        if self.klt_fb_max > 0.0:
+            uv, st, _ = klt_fb_host(self.klt, prev, cur, pts, self.klt_fb_max)
+        else:
+            uv, st = self.klt(prev, cur, pts)
         H, W = imgs[2]
         keep = (st == 1) & in_margin(uv, W, H)
         xr = np.zeros(len(uv), np.float32)
@@ -586,6 +615,12 @@ class GPUBackend(Backend):
         dres = self._dbuf("res", 14 * n)
         c.copy_async(d_in, hp, 8 * n)
         kp = klt_params()
+        if self.klt_fb_max > 0.0:  # the combined status lands in the byte the matcher gates on
+            c.check(c.lib.me_klt_track_fb(c.h, ME_DEVICE, ctypes.c_void_p(prev[0]), ctypes.c_void_p(cur[0]), W, H, W,
+                                          ctypes.c_void_p(d_in), ctypes.c_void_p(dres),
+                                          ctypes.c_void_p(dres + 12 * n), None, n, ctypes.byref(kp),
+                                          float(self.klt_fb_max)), "me_klt_track_fb")
+            return (n, prev, cur)
         c.check(c.lib.me_klt_track(c.h, ME_DEVICE, ctypes.c_void_p(prev[0]), ctypes.c_void_p(cur[0]), W, H, W,
                                    ctypes.c_void_p(d_in), ctypes.c_void_p(dres), ctypes.c_void_p(dres + 12 * n), n,
                                    ctypes.byref(kp)), "me_klt_track")
@@ -998,6 +1033,7 @@ class WindowedStereoVO:
         self.be = backend
         self.be.d_max = cfg.d_max
         self.be.detector = (cfg.detector, cfg.corner_win, cfg.corner_min_eig)
+        self.be.klt_fb_max = float(cfg.klt_fb_max)
         if hasattr(backend, "reserve"):
             backend.reserve(cfg)
         self.K = np.asarray(S.intrinsics(cfg.width, cfg.height) if K is None else K, np.float64)
@@ -1502,6 +1538,7 @@ class NativeStereoVO:
         c.async_enqueue = int(async_enqueue)
         c.detector = DETECTORS.index(cfg.detector)
         c.corner_win, c.corner_min_eig = int(cfg.corner_win), float(cfg.corner_min_eig)
+        c.klt_fb_max = float(cfg.klt_fb_max)
         h = ctypes.c_void_p()
         self.ctx.check(self.lib.me_vo_loop_create(self.ctx.h, self.tctx.h, ctypes.byref(c), ctypes.byref(h)),
                        "me_vo_loop_create")
