@@ -864,6 +864,12 @@ class WindowedStereoVO {
   }
   WindowedStereoVO(const WindowedStereoVO&) = delete;
   WindowedStereoVO& operator=(const WindowedStereoVO&) = delete;
+  // The left-right check of the loop's stereo matches (me_hip.h A2b): lrMax > 0
+  // switches it on with that bound in disparity pixels, 0 off (the default).
+  // Before the first process(); a negative or NaN bound, or a later call, throws.
+  void setMatchLrMax(double lrMax) {
+    check(me_vo_loop_set_match_lr(v_.get(), lrMax), "WindowedStereoVO::setMatchLrMax");
+  }
   // keyframe t (0, 1, 2, ...): host images of the configured size, copied in
   void process(int t, const amd::ImageView& left, const amd::ImageView& right) {
     if (left.empty() || right.empty() || left.step != left.cols || right.step != right.cols)

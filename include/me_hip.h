@@ -147,6 +147,43 @@ int me_mi_epipolar_match_count(me_ctx* ctx, const uint8_t* imgL, const uint8_t* 
                                int stride, const float* uv, const int32_t* lo, const int32_t* n_dev, int n_max,
                                int nd, int patch, int d_max, int unique, double ratio, float margin, float* xr_out,
                                uint8_t* ok_out);
+/* ---- A2b: left-right consistency check of the epipolar matcher (build-
+ * defined; no reference symbol) -- the stereo twin of me_klt_track_fb: match
+ * left -> right, match the right patch that won back into the left image
+ * over the same disparity candidates, keep the match only if the way back
+ * arrives at the same disparity.  With P = patch, half = patch / 2,
+ * x0 = floor((double)u - half), y0 likewise, d_c = lo_f + c, c = 0 .. nd - 1:
+ *  1. forward: me_mi_epipolar_match with the same arguments.  xr_out is its
+ *     xr_out bit for bit for every feature, ok_f its ok_out; kk is its clamped
+ *     pick index and disp_f = (double)(lo_f + kk) + delta its FP64 disparity.
+ *  2. backward, only for features with ok_f = 1: the template is the right
+ *     patch at the integer winner, corner (xb, y0), xb = x0 - (lo_f + kk);
+ *     candidate c is the left patch with corner (xb + d_c, y0) = (x0 + c - kk,
+ *     y0); its score is the MI of (that left patch, the template) in
+ *     me_mi_scores argument order, computed iff d_c <= d_max, xb + d_c >= 0
+ *     and xb + d_c + P <= width, -inf otherwise.  Candidate c = kk is the
+ *     forward winner's own pair: the forward score, bit for bit.
+ *  3. backward pick: the forward pick's rule with unique = 0 and without the
+ *     xr >= margin test (first maximum, interior, finite best and neighbours,
+ *     negative curvature, the same FP64 parabola): ok_b and
+ *     disp_b = (double)(lo_f + kk_b) + delta_b.
+ *  4. gate, FP64, no contraction: a = fabs(disp_b - disp_f);
+ *     ok_out = 1 iff ok_f && ok_b && a <= lr_max; lr_err (n floats, may be
+ *     NULL) = (float)a, rounded to nearest, when ok_f && ok_b, +inf otherwise.
+ * lr_max must be > 0 (NaN, 0, negative: ME_ERR_INVALID); +inf accepts every
+ * feature both passes matched.  The other argument checks are the plain
+ * call's; n = 0 is allowed.  Device memory, asynchronous on the ctx stream;
+ * timed in the ME_KT_MI family.  The numpy restatement is
+ * pipeline.match_lr_host.  The _count form is to me_mi_epipolar_match_count
+ * what the first is to me_mi_epipolar_match. */
+int me_mi_epipolar_match_lr(me_ctx* ctx, const uint8_t* imgL, const uint8_t* imgR, int width, int height, int stride,
+                            const float* uv, const int32_t* lo, const uint8_t* valid, const uint8_t* status, int n,
+                            int nd, int patch, int d_max, int unique, double ratio, float margin, double lr_max,
+                            float* xr_out, uint8_t* ok_out, float* lr_err);
+int me_mi_epipolar_match_lr_count(me_ctx* ctx, const uint8_t* imgL, const uint8_t* imgR, int width, int height,
+                                  int stride, const float* uv, const int32_t* lo, const int32_t* n_dev, int n_max,
+                                  int nd, int patch, int d_max, int unique, double ratio, float margin, double lr_max,
+                                  float* xr_out, uint8_t* ok_out, float* lr_err);
 /* New-feature cells of the VO loop (pipeline.new_cells on the device; no
    reference symbol -- the application's grid detector around WBA_Point
    creation): tracked feature k is good iff status_k == 1, ok_k != 0 and it
@@ -430,6 +467,12 @@ void me_vo_loop_default_config(me_vo_loop_config* c);
 int me_vo_loop_create(me_ctx* ba, me_ctx* front, const me_vo_loop_config* cfg, me_vo_loop** out);
 void me_vo_loop_destroy(me_vo_loop* v);
 const char* me_vo_loop_last_error(const me_vo_loop* v);
+/* The left-right check of the loop's stereo matches (A2b): lr_max > 0 makes
+   every matcher call of the loop its _lr form with that bound (disparity
+   pixels); 0 (the default) switches it off.  NaN or negative: ME_ERR_INVALID;
+   after the first me_vo_loop_process: ME_ERR_STATE.  (A setter, not a
+   me_vo_loop_config field: the struct and the ABI version stay as they are.) */
+int me_vo_loop_set_match_lr(me_vo_loop* v, double lr_max);
 /* Keyframe t (t = 0, 1, 2, ... in order): left / right 8-bit images of
    width x height (stride = width).  mem = ME_DEVICE: device memory on the
    ctx device, read during this call and the next one (keep it alive until

@@ -18,6 +18,10 @@ loads another build of libme_hip.so (tools/build_variant.sh).
   klt_fb [--reps --repeats --check --loop N]
                          me_klt_track_fb beside me_klt_track on the config-3 frame (2000 features), alternating
                          in one process, and the config-3 native loop with klt_fb_max 0 / 0.5, alternating
+  match_lr [--reps --repeats --check --loop N --plain-only]
+                         me_mi_epipolar_match_lr beside me_mi_epipolar_match on a config-3 stereo pair (2000
+                         tracked-form and 250 new-form features), alternating in one process, and the config-3
+                         native loop with match_lr_max 0 / 1, alternating
 """
 import argparse
 import ctypes
@@ -553,6 +557,157 @@ def cmd_klt_fb(a):
     print(json.dumps(out))
 
 
+def cmd_match_lr(a):
+    """The left-right check (csrc/mi.hip, me_mi_epipolar_match_lr) beside the
+    plain matcher on a config-3 stereo pair, in the loop's two forms: 2000
+    tracked-form features (nd = 13 around the synthetic disparity, unique = 0)
+    and 250 new-form features (nd = 127 from d_min, unique = 1).  Per call the
+    ME_KT_MI events (plain: scores and pick; check: both passes under one event
+    pair) and the host wall time, --repeats blocks of --reps calls each, the
+    two entry points alternating (--plain-only: the plain one alone, for an
+    A/B of two builds).  Then (--loop N) the native VO loop at config 3 over N
+    corridor keyframes with match_lr_max 0 and --lr-max, alternating, two
+    repeats each."""
+    from uasl_motion_estimation_amd import pipeline as PL
+    from uasl_motion_estimation_amd import synthetic as S
+    ctx = _setup(a.lib)
+    V = ctypes.c_void_p
+    W, H, D_MIN, D_MAX = 1280, 720, 2, 128
+    scene, K, stream = S.stereo_stream(20261018, W, H, 1)
+    L, R = np.ascontiguousarray(stream[0].left), np.ascontiguousarray(stream[0].right)
+    dL, dR = ctx.malloc(W * H), ctx.malloc(W * H)
+    ctx.h2d(dL, L)
+    ctx.h2d(dR, R)
+    forms = {}
+    for name, n, nd, unique, seed in (("tracked", 2000, 13, 0, 0), ("new", 250, 127, 1, 1)):
+        uv = S.grid_features(np.random.default_rng(seed), n, W, H, PL.MARGIN).astype(np.float32)
+        if unique:
+            lo = np.full(n, D_MIN, np.int32)
+        else:  # the loop's window: +-6 px around the predicted (here: the true) disparity
+            z, _ = S.depth_at(scene, K, stream[0].R, stream[0].t, uv[:, 0].astype(np.float64),
+                              uv[:, 1].astype(np.float64))
+            lo = np.clip(np.rint(K[0, 0] * S.BASELINE / z).astype(np.int64) - 6, D_MIN, D_MAX).astype(np.int32)
+        d = {"n": n, "nd": nd, "unique": unique, "uv": uv, "lo": lo, "duv": ctx.malloc(8 * n), "dlo": ctx.malloc(4 * n),
+             "dxr": ctx.malloc(4 * n), "dok": ctx.malloc(n), "derr": ctx.malloc(4 * n)}
+        ctx.h2d(d["duv"], uv)
+        ctx.h2d(d["dlo"], lo)
+        forms[name] = d
+
+    def plain(d):
+        ctx.check(ctx.lib.me_mi_epipolar_match(ctx.h, V(dL), V(dR), W, H, W, V(d["duv"]), V(d["dlo"]), None, None,
+                                               d["n"], d["nd"], PL.PATCH, D_MAX, d["unique"], 1.2, float(PL.MARGIN),
+                                               V(d["dxr"]), V(d["dok"])), "me_mi_epipolar_match")
+
+    def lr(d):
+        ctx.check(ctx.lib.me_mi_epipolar_match_lr(ctx.h, V(dL), V(dR), W, H, W, V(d["duv"]), V(d["dlo"]), None, None,
+                                                  d["n"], d["nd"], PL.PATCH, D_MAX, d["unique"], 1.2, float(PL.MARGIN),
+                                                  a.lr_max, V(d["dxr"]), V(d["dok"]), V(d["derr"])),
+                  "me_mi_epipolar_match_lr")
+    calls = [("me_mi_epipolar_match", plain)] + ([] if a.plain_only else [("me_mi_epipolar_match_lr", lr)])
+    out = {"inputs": f"{W}x{H}, tracked 2000 x 13 (unique 0), new 250 x 127 (unique 1), lr_max {a.lr_max}",
+           "reps": a.reps, "calls": []}
+    for _, fn in calls:
+        for d in forms.values():
+            for _ in range(5):
+                fn(d)
+    ctx.synchronize()
+    for rep in range(a.repeats):
+        for name, fn in calls:
+            for form, d in forms.items():
+                ctx.timing_reset()
+                ctx.timing(True, ["MI"])
+                w0 = time.perf_counter()
+                for _ in range(a.reps):
+                    fn(d)
+                ctx.synchronize()
+                wall = (time.perf_counter() - w0) / a.reps * 1e6
+                ctx.timing(False)
+                cnt, ms = ctx.timing_read("MI")
+                r = {"call": name, "form": form, "repeat": rep, "wall_us_per_call": round(wall, 2),
+                     "MI_us_per_call": round(1000 * ms / max(cnt, 1), 2), "MI_timed": cnt}
+                out["calls"].append(r)
+                print(json.dumps(r), flush=True)
+    same = True
+    for form, d in forms.items():
+        n = d["n"]
+        (lr if not a.plain_only else plain)(d)
+        ctx.synchronize()
+        gxr, gok, gerr = np.zeros(n, np.float32), np.zeros(n, np.uint8), np.full(n, np.inf, np.float32)
+        ctx.d2h(gxr, d["dxr"])
+        ctx.d2h(gok, d["dok"])
+        if not a.plain_only:
+            ctx.d2h(gerr, d["derr"])
+        counts = {"features": n, "accepted": int(gok.sum())}
+        if not a.plain_only:
+            counts.update(both_passes_matched=int(np.isfinite(gerr).sum()), within_1px=int((gerr <= 1.0).sum()))
+        if a.check:
+            sys.path.insert(0, os.path.join(ROOT, "tests"))
+            from pipeline_oracle import OracleBackend  # checker only
+            ob = OracleBackend()
+            oimgs = ob.frame_images(0, L, R)
+            lo64 = d["lo"].astype(np.int64)
+            if a.plain_only:
+                xr, ok = PL.match_host(ob, oimgs, d["uv"], lo64, d["nd"], None, bool(d["unique"]), D_MAX)
+                ok_f, eq = ok, np.array_equal(gok, ok.astype(np.uint8))
+            else:
+                xr, ok, err, ok_f, ok_b = PL.match_lr_host(ob, oimgs, d["uv"], lo64, d["nd"], None, bool(d["unique"]),
+                                                           D_MAX, a.lr_max)
+                eq = (np.array_equal(gok, ok.astype(np.uint8))
+                      and np.array_equal(gerr.view(np.uint32), err.view(np.uint32)))
+                counts.update(forward_accepted=int(ok_f.sum()))
+            eq = eq and np.array_equal(gxr.view(np.uint32)[ok_f], xr.view(np.uint32)[ok_f])
+            print(f"match_lr parity vs the restatement, {form}: {'bit-exact' if eq else 'MISMATCH'} {counts}",
+                  flush=True)
+            same = same and eq
+        out[form] = counts
+    for d in forms.values():
+        for k in ("duv", "dlo", "dxr", "dok", "derr"):
+            ctx.free(d[k])
+    ctx.free(dL)
+    ctx.free(dR)
+    if not same:
+        sys.exit(1)
+    if a.loop > 0 and not a.plain_only:
+        import torch
+
+        c, NK = 3, a.loop
+        arc = S.trajectory_arc(max(NK, 2))
+        truth = [np.concatenate([t, S.R_to_aa_robust(Rm)]) for (Rm, t) in arc]
+        K = S.intrinsics(1280, 720)
+        frames = []
+        for c0 in range(0, NK, 50):
+            _, fr = S.corridor_frames_torch(S.SEED0 + c, 1280, 720, c0, min(50, NK - c0))
+            frames += [(Lk.contiguous(), Rk.contiguous()) for (Lk, Rk, _, _) in fr]
+            torch.cuda.synchronize()
+            print(f"rendered {len(frames)} keyframes", flush=True)
+        runs = []
+        for rep in range(-1, 2):  # (-1: a short untimed run, the first loop of a process pays the allocations)
+            for lr_max in (0.0, a.lr_max):
+                cfg = PL.PipelineConfig.from_config(c, match_lr_max=lr_max)
+                vo = PL.NativeStereoVO(cfg, ctx, K, truth[0], truth[1] - truth[0], log_events=False, overlap=True)
+                t0 = time.perf_counter()
+                for t in range(NK if rep >= 0 else min(NK, 30)):
+                    vo.process(t, *frames[t])
+                vo.finish()
+                dt = time.perf_counter() - t0
+                if rep < 0:
+                    vo.close()
+                    continue
+                st = vo._stats()
+                res = vo.results
+                vo.close()
+                names = ["klt_match", "first_match", "scale_submit", "window_submit", "ba_result", "scale_result"]
+                r = {"match_lr_max": lr_max, "repeat": rep, "keyframes": NK, "keyframes_per_s": round(NK / dt, 2),
+                     "tracked_mean": round(float(np.mean([q.n_tracked for q in res[2:]])), 1),
+                     "new_mean": round(float(np.mean([q.n_new for q in res[2:]])), 1),
+                     "host_s": round(st[0], 4), "blocked_s": round(st[1], 4),
+                     "wait_ms_per_keyframe": {k: round(1e3 * st[3 + i] / NK, 4) for i, k in enumerate(names)}}
+                runs.append(r)
+                print(json.dumps(r), flush=True)
+        out["loop_config3"] = runs
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--lib", default=os.environ.get("ME_LIB"))
@@ -587,6 +742,14 @@ def main():
     p.add_argument("--fb-max", dest="fb_max", type=float, default=0.5)
     p.add_argument("--check", type=int, default=1)
     p.add_argument("--loop", type=int, default=200, help="keyframes of the config-3 native loop per run (0: skip)")
+    p = sub.add_parser("match_lr")
+    p.add_argument("--reps", type=int, default=200)
+    p.add_argument("--repeats", type=int, default=3)
+    p.add_argument("--lr-max", dest="lr_max", type=float, default=1.0)
+    p.add_argument("--check", type=int, default=1)
+    p.add_argument("--loop", type=int, default=200, help="keyframes of the config-3 native loop per run (0: skip)")
+    p.add_argument("--plain-only", dest="plain_only", action="store_true",
+                   help="me_mi_epipolar_match alone (works on a build without the check: A/B of two trees)")
     a = ap.parse_args()
     globals()["cmd_" + a.cmd](a)
 

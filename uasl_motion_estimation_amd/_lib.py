@@ -159,7 +159,7 @@ EXPORTS = [
     "me_get_stream", "me_set_cu_mask", "me_stream_flags", "me_cu_count", "me_synchronize", "me_malloc", "me_free", "me_memcpy_h2d", "me_memcpy_d2h", "me_memcpy_d2d",
     "me_memcpy_async", "me_host_alloc", "me_host_free", "me_hbm_copy_gbs",
     "me_timing_enable", "me_timing_read", "me_timing_reset", "me_timing_sample",
-    "me_mi_scores", "me_mutual_information", "me_entropy", "me_mi_epipolar_match", "me_mi_epipolar_match_count", "me_vo_new_cells", "me_compare_pc", "me_ccoeff_normed", "me_quantise",
+    "me_mi_scores", "me_mutual_information", "me_entropy", "me_mi_epipolar_match", "me_mi_epipolar_match_count", "me_mi_epipolar_match_lr", "me_mi_epipolar_match_lr_count", "me_vo_new_cells", "me_compare_pc", "me_ccoeff_normed", "me_quantise",
     "me_optim_default_params", "me_scale_residuals", "me_scale_normal_equations", "me_scale_jacobian",
     "me_scale_optimise", "me_scale_last_counters", "me_scale_persistent", "me_scale_state_mi", "me_scale_inliers",
     "me_ba_default_options", "me_ba_solve", "me_ba_cost", "me_ba_evaluate", "me_ba_reduced_system",
@@ -174,7 +174,7 @@ EXPORTS = [
     "me_mono_default_params", "me_mono_vo_process",
     "me_vo_loop_default_config", "me_vo_loop_create", "me_vo_loop_destroy", "me_vo_loop_last_error",
     "me_vo_loop_process", "me_vo_loop_finish", "me_vo_loop_results", "me_vo_loop_events", "me_vo_loop_tracks",
-    "me_vo_loop_poses", "me_vo_loop_frame_obs", "me_vo_loop_frames", "me_vo_loop_stats",
+    "me_vo_loop_poses", "me_vo_loop_frame_obs", "me_vo_loop_frames", "me_vo_loop_stats", "me_vo_loop_set_match_lr",
 ]
 
 class MonoParamsC(ctypes.Structure):
@@ -246,6 +246,12 @@ def load_library(path: str | None = None):
         "me_mi_epipolar_match_count": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
                                                c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_double,
                                                c_float, c_void_p, c_void_p]),
+        "me_mi_epipolar_match_lr": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                            c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_double, c_float,
+                                            c_double, c_void_p, c_void_p, c_void_p]),
+        "me_mi_epipolar_match_lr_count": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                                  c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_double,
+                                                  c_float, c_double, c_void_p, c_void_p, c_void_p]),
         "me_vo_new_cells": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_int,
                                     c_double, c_double, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
         "me_compare_pc": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
@@ -296,6 +302,7 @@ def load_library(path: str | None = None):
         "me_vo_loop_default_config": (None, [P(VOLoopConfigC)]),
         "me_vo_loop_create": (c_int, [c_void_p, c_void_p, P(VOLoopConfigC), P(c_void_p)]),
         "me_vo_loop_destroy": (None, [c_void_p]),
+        "me_vo_loop_set_match_lr": (c_int, [c_void_p, c_double]),
         "me_vo_loop_last_error": (ctypes.c_char_p, [c_void_p]),
         "me_vo_loop_process": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int]),
         "me_vo_loop_finish": (c_int, [c_void_p]),

@@ -149,8 +149,26 @@ struct EpiMap {
   double* sc;  // n x nd scores
 };
 
+// Backward pass of the left-right check (me_hip.h A2b, BACK instances): `back`
+// holds the per-feature {kk, ok_f} the forward pick left (the lane and quad
+// kernels take it in their xyL argument, which EPI instances do not use
+// otherwise: the plain instances keep their arguments and code).  The
+// template is the right patch of the forward winner, corner xb = x0 - (lo_f +
+// kk); candidate c is the left patch d = lo_f + c pixels to its right, corner
+// xl = xb + d = x0 + c - kk; scored iff the forward pass accepted the feature
+// (so both y0 rows and, for lo_f + kk >= 0, the template lie inside the
+// image), d <= d_max and the left patch lies inside the row.  The test on xb
+// itself only keeps a negative disparity's template inside the row.
+__device__ __forceinline__ bool epi_back_pair(const int32_t* __restrict__ back, int f, int d, int lo_f, int x0,
+                                              int d_max, int width, int patch, int& xl, int& xb) {
+  const int2 r = reinterpret_cast<const int2*>(back)[f];
+  xb = x0 - (lo_f + r.x);
+  xl = xb + d;
+  return r.y != 0 && d <= d_max && xl >= 0 && xl + patch <= width && xb >= 0 && xb + patch <= width;
+}
+
 // PW, PH > 0: patch size known at compile time (11x11 residual, 10x10 finite-difference ROIs).
-template <int PW, int PH, bool EPI = false>
+template <int PW, int PH, bool EPI = false, bool BACK = false>
 __global__ __launch_bounds__(kLaneBlock) void mi_lane_kernel(const uint8_t* __restrict__ imgL, int strideL,
                                                              const uint8_t* __restrict__ imgR, int strideR,
                                                              long bytesL, long bytesR,
@@ -178,12 +196,20 @@ __global__ __launch_bounds__(kLaneBlock) void mi_lane_kernel(const uint8_t* __re
       if (em.status)  // the KLT gate: status 1 and inside the feature margin
         fv = fv && em.status[f] == 1 && u >= em.margin && u < (float)em.width - em.margin && v >= em.margin &&
              v < (float)em.height - em.margin;
-      const int d = em.lo[f] + c, xr = x0 - d;
-      // (inside the image: the left patch, and the right one (x >= 0) -- ADVICE r3)
-      live = fv && xr >= 0 && d <= em.d_max && x0 >= 0 && y0 >= 0 && x0 + 2 * em.half + 1 <= em.width &&
-             y0 + 2 * em.half + 1 <= em.height;
-      oL = (long)y0 * strideL + x0;
-      oR = (long)y0 * strideR + xr;
+      if constexpr (BACK) {  // (a feature the forward pass refused: no pair scored, whatever uv holds)
+        int xl, xb;
+        const int lo_f = em.lo[f];
+        live = epi_back_pair(xyL, f, lo_f + c, lo_f, x0, em.d_max, em.width, 2 * em.half + 1, xl, xb);
+        oL = (long)y0 * strideL + xl;
+        oR = (long)y0 * strideR + xb;
+      } else {
+        const int d = em.lo[f] + c, xr = x0 - d;
+        // (inside the image: the left patch, and the right one (x >= 0) -- ADVICE r3)
+        live = fv && xr >= 0 && d <= em.d_max && x0 >= 0 && y0 >= 0 && x0 + 2 * em.half + 1 <= em.width &&
+               y0 + 2 * em.half + 1 <= em.height;
+        oL = (long)y0 * strideL + x0;
+        oR = (long)y0 * strideR + xr;
+      }
     } else if (!EPI && live) {
       const int2 cl = reinterpret_cast<const int2*>(xyL)[k];
       const int2 cr = reinterpret_cast<const int2*>(xyR)[k];
@@ -430,7 +456,7 @@ __device__ __forceinline__ void quad_hist(uint32_t* hg, const uint8_t* __restric
   }
 }
 
-template <int PW, int PH, bool EPI = false>
+template <int PW, int PH, bool EPI = false, bool BACK = false>
 __global__ __launch_bounds__(kQuadBlock) void mi_quad_kernel(const uint8_t* __restrict__ imgL, int strideL,
                                                              const uint8_t* __restrict__ imgR, int strideR,
                                                              long bytesL, long bytesR,
@@ -458,12 +484,20 @@ __global__ __launch_bounds__(kQuadBlock) void mi_quad_kernel(const uint8_t* __re
       if (em.status)
         fv = fv && em.status[f] == 1 && u >= em.margin && u < (float)em.width - em.margin && v >= em.margin &&
              v < (float)em.height - em.margin;
-      const int d = em.lo[f] + c, xr = x0 - d;
-      // (inside the image: the left patch, and the right one (x >= 0) -- ADVICE r3)
-      live = fv && xr >= 0 && d <= em.d_max && x0 >= 0 && y0 >= 0 && x0 + 2 * em.half + 1 <= em.width &&
-             y0 + 2 * em.half + 1 <= em.height;
-      oL = (long)y0 * strideL + x0;
-      oR = (long)y0 * strideR + xr;
+      if constexpr (BACK) {  // (a feature the forward pass refused: no pair scored, whatever uv holds)
+        int xl, xb;
+        const int lo_f = em.lo[f];
+        live = epi_back_pair(xyL, f, lo_f + c, lo_f, x0, em.d_max, em.width, 2 * em.half + 1, xl, xb);
+        oL = (long)y0 * strideL + xl;
+        oR = (long)y0 * strideR + xb;
+      } else {
+        const int d = em.lo[f] + c, xr = x0 - d;
+        // (inside the image: the left patch, and the right one (x >= 0) -- ADVICE r3)
+        live = fv && xr >= 0 && d <= em.d_max && x0 >= 0 && y0 >= 0 && x0 + 2 * em.half + 1 <= em.width &&
+               y0 + 2 * em.half + 1 <= em.height;
+        oL = (long)y0 * strideL + x0;
+        oR = (long)y0 * strideR + xr;
+      }
     } else if (!EPI && live) {
       const int2 cl = reinterpret_cast<const int2*>(xyL)[k];
       const int2 cr = reinterpret_cast<const int2*>(xyR)[k];
@@ -818,12 +852,14 @@ inline bool mi_use_lane_kernel(const me_ctx* c) { return (c->dbg_solve_flags & k
 //    (first maximum, interior, parabola vertex, uniqueness against the best
 //    outside +-2 candidates, x_r = u - disparity, margin test).
 // n_dev (optional): the feature count a preceding kernel left on the device.
+// BACK: the backward pass of the left-right check (epi_back_pair).
 constexpr int kEpiMaxNd = 512, kEpiBlock = 256, kEpiGroups = kEpiBlock / 16, kBlockPick = 256;
+template <bool BACK>
 __global__ __launch_bounds__(kEpiBlock) void mi_epi_score_kernel(
     const uint8_t* __restrict__ L, const uint8_t* __restrict__ R, int stride, int width, int height,
     const float* __restrict__ uv, const int32_t* __restrict__ lo, const uint8_t* __restrict__ valid,
     const uint8_t* __restrict__ status, int n, const int32_t* __restrict__ n_dev, int nd, int patch, int d_max,
-    float margin, float invN, double* __restrict__ sc) {
+    float margin, float invN, double* __restrict__ sc, const int32_t* __restrict__ back) {
   __shared__ uint32_t lds[kEpiGroups * kGroupWords];
   const int grp = threadIdx.x >> 4;
   GroupHist<16> h{&lds[grp * kGroupWords], (int)(threadIdx.x & 15)};
@@ -839,31 +875,27 @@ __global__ __launch_bounds__(kEpiBlock) void mi_epi_score_kernel(
     if (status)  // the KLT gate: status 1 and inside the feature margin
       fv = fv && status[f] == 1 && u >= margin && u < (float)width - margin && v >= margin &&
            v < (float)height - margin;
-    const int d = lo[f] + c, xr = x0 - d;
-    const bool ok = fv && xr >= 0 && d <= d_max && x0 >= 0 && y0 >= 0 && x0 + patch <= width &&
-                    y0 + patch <= height;  // (group-uniform; both patches inside the image)
+    int d = lo[f] + c, xl = x0, xr = x0 - d;
+    bool ok;  // (group-uniform; both patches inside the image)
+    if constexpr (BACK)
+      ok = epi_back_pair(back, f, d, d - c, x0, d_max, width, patch, xl, xr);
+    else
+      ok = fv && xr >= 0 && d <= d_max && x0 >= 0 && y0 >= 0 && x0 + patch <= width && y0 + patch <= height;
     float s = 0.0f;
     const long end = (long)(height - 1) * stride + width;  // one past each image's last byte
-    if (ok) s = group_mi<false>(h, L + (long)y0 * stride + x0, stride, R + (long)y0 * stride + xr, stride, patch, patch,
+    if (ok) s = group_mi<false>(h, L + (long)y0 * stride + xl, stride, R + (long)y0 * stride + xr, stride, patch, patch,
                                 invN, nullptr, L + end, R + end);
     if (h.gl == 0) sc[q] = ok ? (double)s : -INFINITY;
   }
 }
 
-// One wave per feature: lanes take candidates lane, lane + 64, ...; the first
-// maximum (largest score, smallest index on ties: np.argmax) and the best
+// The pick of one feature's nd scores, shared by the forward and the backward
+// pass of the left-right check (so the two cannot round differently).
+// epi_argmax, the whole wave: lanes take candidates lane, lane + 64, ...; the
+// first maximum (largest score, smallest index on ties: np.argmax) and the best
 // outside +-2 candidates by wave reductions (exact: max / compare only).
-__global__ __launch_bounds__(kBlockPick) void mi_epi_pick_kernel(const float* __restrict__ uv,
-                                                                 const int32_t* __restrict__ lo, int n,
-                                                                 const int32_t* __restrict__ n_dev, int nd, int unique,
-                                                                 double ratio, float margin,
-                                                                 const double* __restrict__ scores,
-                                                                 float* __restrict__ xr_out,
-                                                                 uint8_t* __restrict__ ok_out) {
-  const int lane = threadIdx.x & 63;
-  const int f = blockIdx.x * (kBlockPick / 64) + (threadIdx.x >> 6);
-  if (f >= (n_dev ? min(n, *n_dev) : n)) return;  // (wave-uniform)
-  const double* sc = scores + (long)f * nd;
+__device__ __forceinline__ void epi_argmax(const double* __restrict__ sc, int nd, int unique, int lane, int& k,
+                                           double& best, double& second) {
   double bv = -INFINITY;
   int bi = nd;  // (no score above -inf: np.argmax gives 0)
   for (int c = lane; c < nd; c += 64) {
@@ -882,16 +914,25 @@ __global__ __launch_bounds__(kBlockPick) void mi_epi_pick_kernel(const float* __
       bi = oi;
     }
   }
-  const int k = bi == nd ? 0 : bi;
-  const double best = bi == nd ? -INFINITY : bv;
-  double second = -INFINITY;
+  k = bi == nd ? 0 : bi;
+  best = bi == nd ? -INFINITY : bv;
+  second = -INFINITY;
   if (unique) {
     for (int c = lane; c < nd; c += 64)
       if (c < k - 2 || c > k + 2) second = fmax(second, sc[c]);
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) second = fmax(second, __shfl_xor(second, off, 64));
   }
-  if (lane != 0) return;
+}
+// epi_vertex, one lane: interior, finite, FP64 parabola vertex, uniqueness;
+// kk = the clamped pick index, disp = lo_f + kk + delta (no margin test).
+struct EpiPick {
+  bool ok;
+  int kk;
+  double disp;
+};
+__device__ __forceinline__ EpiPick epi_vertex(const double* __restrict__ sc, int nd, int unique, double ratio, int k,
+                                              double best, double second, int lo_f) {
   bool ok = k > 0 && k < nd - 1 && isfinite(best);
   const int kk = min(max(k, 1), nd - 2);
   const double sm = sc[kk - 1], s0 = sc[kk], sp = sc[kk + 1];
@@ -900,61 +941,143 @@ __global__ __launch_bounds__(kBlockPick) void mi_epi_pick_kernel(const float* __
   if (unique) ok = ok && best >= ratio * second;
   const double den_s = ok ? den : -1.0;
   const double delta = ok ? 0.5 * (sm - sp) / den_s : 0.0;
-  const double disp = (double)(lo[f] + kk) + delta;
-  const float xr_f = (float)((double)uv[2 * f] - disp);
-  ok = ok && xr_f >= margin;
+  return EpiPick{ok, kk, (double)(lo_f + kk) + delta};
+}
+
+// One wave per feature.  LR (me_mi_epipolar_match_lr): the pick also leaves
+// {kk, ok} in back[2 f] and its FP64 disparity in disp_f[f] for the way back.
+template <bool LR>
+__global__ __launch_bounds__(kBlockPick) void mi_epi_pick_kernel(const float* __restrict__ uv,
+                                                                 const int32_t* __restrict__ lo, int n,
+                                                                 const int32_t* __restrict__ n_dev, int nd, int unique,
+                                                                 double ratio, float margin,
+                                                                 const double* __restrict__ scores,
+                                                                 float* __restrict__ xr_out,
+                                                                 uint8_t* __restrict__ ok_out,
+                                                                 int32_t* __restrict__ back,
+                                                                 double* __restrict__ disp_f) {
+  const int lane = threadIdx.x & 63;
+  const int f = blockIdx.x * (kBlockPick / 64) + (threadIdx.x >> 6);
+  if (f >= (n_dev ? min(n, *n_dev) : n)) return;  // (wave-uniform)
+  const double* sc = scores + (long)f * nd;
+  int k;
+  double best, second;
+  epi_argmax(sc, nd, unique, lane, k, best, second);
+  if (lane != 0) return;
+  const EpiPick p = epi_vertex(sc, nd, unique, ratio, k, best, second, lo[f]);
+  const float xr_f = (float)((double)uv[2 * f] - p.disp);
+  const bool ok = p.ok && xr_f >= margin;
   xr_out[f] = xr_f;
   ok_out[f] = ok ? 1 : 0;
+  if constexpr (LR) {
+    reinterpret_cast<int2*>(back)[f] = make_int2(p.kk, ok ? 1 : 0);
+    disp_f[f] = p.disp;
+  }
+}
+
+// The way back of the left-right check, one wave per feature the forward pass
+// accepted: the forward pick's rule (unique = 0, no margin test) over the
+// backward scores, then the gate |disp_b - disp_f| <= lr_max in FP64.
+__global__ __launch_bounds__(kBlockPick) void mi_epi_back_pick_kernel(const int32_t* __restrict__ lo, int n,
+                                                                      const int32_t* __restrict__ n_dev, int nd,
+                                                                      const double* __restrict__ scores,
+                                                                      const int32_t* __restrict__ back,
+                                                                      const double* __restrict__ disp_f,
+                                                                      double lr_max, uint8_t* __restrict__ ok_out,
+                                                                      float* __restrict__ lr_err) {
+  const int lane = threadIdx.x & 63;
+  const int f = blockIdx.x * (kBlockPick / 64) + (threadIdx.x >> 6);
+  if (f >= (n_dev ? min(n, *n_dev) : n)) return;  // (wave-uniform)
+  if (reinterpret_cast<const int2*>(back)[f].y == 0) {  // (wave-uniform: ok_out is the forward pass's 0)
+    if (lane == 0 && lr_err) lr_err[f] = INFINITY;
+    return;
+  }
+  const double* sc = scores + (long)f * nd;
+  int k;
+  double best, second;
+  epi_argmax(sc, nd, 0, lane, k, best, second);
+  if (lane != 0) return;
+  const EpiPick p = epi_vertex(sc, nd, 0, 0.0, k, best, second, lo[f]);
+  const double a = fabs(p.disp - disp_f[f]);
+  ok_out[f] = p.ok && a <= lr_max ? 1 : 0;
+  if (lr_err) lr_err[f] = p.ok ? (float)a : INFINITY;
 }
 
 }  // namespace
 
+// The candidate scores of one pass (BACK: the way back of the left-right check) into sc.
+template <bool BACK>
+static int epi_score_launch(me_ctx* c, const uint8_t* imgL, const uint8_t* imgR, int width, int height, int stride,
+                            const float* uv, const int32_t* lo, const uint8_t* valid, const uint8_t* status, int n,
+                            const int32_t* n_dev, int nd, int patch, int d_max, float margin, const float* tab,
+                            double* sc, const int32_t* back) {
+  const long pairs = (long)n * nd;
+  if (patch == 11) {
+    // one lane per candidate pair (table-driven terms, the batch kernel's bits)
+    EpiMap em{uv, lo, valid, status, n_dev, nd, d_max, width, height, patch / 2, margin, sc};
+    const long img_bytes = (long)stride * (height - 1) + width;
+    if (!mi_use_lane_kernel(c)) {
+      const int qb = (int)std::min<long>((pairs + kQuadGroups - 1) / kQuadGroups, 16384);
+      hipLaunchKernelGGL((mi_quad_kernel<11, 11, true, BACK>), dim3(qb), dim3(kQuadBlock), 0, c->stream, imgL, stride,
+                         imgR, stride, img_bytes, img_bytes, back, nullptr, n, 11, 11, tab,
+                         (int)(4 * mi_tab_size(121)), nullptr, em);
+      return me_check_launch(c, "mi_quad_kernel<epi>");
+    }
+    const int blocks = (int)std::min<long>((pairs + kLaneBlock - 1) / kLaneBlock, 8192);
+    hipLaunchKernelGGL((mi_lane_kernel<11, 11, true, BACK>), dim3(blocks), dim3(kLaneBlock), 0, c->stream, imgL, stride,
+                       imgR, stride, img_bytes, img_bytes, back, nullptr, n, 11, 11, tab,
+                       (int)(4 * mi_tab_size(121)), nullptr, em);
+    return me_check_launch(c, "mi_lane_kernel<epi>");
+  }
+  // grid-stride over n x nd 16-lane groups: at most ~8 workgroups per CU (28 KB of LDS each)
+  const int blocks = (int)std::min<long>((pairs + kEpiGroups - 1) / kEpiGroups, 8L * std::max(c->num_cu, 1));
+  hipLaunchKernelGGL(mi_epi_score_kernel<BACK>, dim3(blocks), dim3(kEpiBlock), 0, c->stream, imgL, imgR, stride, width,
+                     height, uv, lo, valid, status, n, n_dev, nd, patch, d_max, margin,
+                     inv_count((long)patch * patch), sc, back);
+  return me_check_launch(c, "mi_epi_score_kernel");
+}
+
+// lr: the left-right check (me_hip.h A2b) -- forward scores and pick as the
+// plain call, then the backward scores over the same block (the forward scores
+// are dead after their pick) and the backward pick with the gate.  Scratch:
+// n x nd scores | n x {kk, ok_f} | n forward disparities.
 static int epipolar_launch(me_ctx* c, const uint8_t* imgL, const uint8_t* imgR, int width, int height, int stride,
                            const float* uv, const int32_t* lo, const uint8_t* valid, const uint8_t* status, int n,
                            const int32_t* n_dev, int nd, int patch, int d_max, int unique, double ratio, float margin,
-                           float* xr_out, uint8_t* ok_out) {
+                           float* xr_out, uint8_t* ok_out, bool lr = false, double lr_max = 0.0,
+                           float* lr_err = nullptr) {
   if (!c) return ME_ERR_INVALID;
   ME_CHECK(c, n >= 0 && nd >= 3 && nd <= kEpiMaxNd && patch > 0 && patch * patch <= 255 && width > 0 && height > 0 &&
                   stride >= width,
            "me_mi_epipolar_match: bad sizes (3 <= nd <= %d, patch <= 15)", kEpiMaxNd);
+  if (lr) ME_CHECK(c, lr_max > 0.0, "me_mi_epipolar_match_lr: lr_max must be > 0 (+inf: no bound)");  // (false for NaN)
   if (n == 0) return ME_OK;
   ME_HIP(c, hipSetDevice(c->device));
   ME_CHECK(c, (long)n * nd < (1L << 31), "me_mi_epipolar_match: too many candidates");
-  void* sc;
-  ME_TRY(me_scratch(c, SLOT_EPI, 8 * (size_t)n * nd, &sc));
+  void* scp;
+  ME_TRY(me_scratch(c, SLOT_EPI, 8 * (size_t)n * nd + (lr ? 16 * (size_t)n : 0), &scp));
+  double* sc = (double*)scp;
   const float* tab = nullptr;
   if (patch == 11) ME_TRY(me_mi_table(c, 121, &tab));
   me_ktimer t(c, ME_KT_MI);
-  const long pairs = (long)n * nd;
-  if (patch == 11) {
-    // one lane per candidate pair (table-driven terms, the batch kernel's bits)
-    EpiMap em{uv, lo, valid, status, n_dev, nd, d_max, width, height, patch / 2, margin, (double*)sc};
-    const long img_bytes = (long)stride * (height - 1) + width;
-    if (!mi_use_lane_kernel(c)) {
-      const int qb = (int)std::min<long>((pairs + kQuadGroups - 1) / kQuadGroups, 16384);
-      hipLaunchKernelGGL((mi_quad_kernel<11, 11, true>), dim3(qb), dim3(kQuadBlock), 0, c->stream, imgL, stride, imgR,
-                         stride, img_bytes, img_bytes, nullptr, nullptr, n, 11, 11, tab, (int)(4 * mi_tab_size(121)),
-                         nullptr, em);
-      ME_TRY(me_check_launch(c, "mi_quad_kernel<epi>"));
-    } else {
-      const int blocks = (int)std::min<long>((pairs + kLaneBlock - 1) / kLaneBlock, 8192);
-      hipLaunchKernelGGL((mi_lane_kernel<11, 11, true>), dim3(blocks), dim3(kLaneBlock), 0, c->stream, imgL, stride,
-                         imgR, stride, img_bytes, img_bytes, nullptr, nullptr, n, 11, 11, tab,
-                         (int)(4 * mi_tab_size(121)), nullptr, em);
-      ME_TRY(me_check_launch(c, "mi_lane_kernel<epi>"));
-    }
-  } else {
-    // grid-stride over n x nd 16-lane groups: at most ~8 workgroups per CU (28 KB of LDS each)
-    const int blocks = (int)std::min<long>((pairs + kEpiGroups - 1) / kEpiGroups, 8L * std::max(c->num_cu, 1));
-    hipLaunchKernelGGL(mi_epi_score_kernel, dim3(blocks), dim3(kEpiBlock), 0, c->stream, imgL, imgR, stride, width,
-                       height, uv, lo, valid, status, n, n_dev, nd, patch, d_max, margin,
-                       inv_count((long)patch * patch), (double*)sc);
-    ME_TRY(me_check_launch(c, "mi_epi_score_kernel"));
+  ME_TRY(epi_score_launch<false>(c, imgL, imgR, width, height, stride, uv, lo, valid, status, n, n_dev, nd, patch,
+                                 d_max, margin, tab, sc, nullptr));
+  const dim3 pick_grid((n + kBlockPick / 64 - 1) / (kBlockPick / 64));
+  if (!lr) {
+    hipLaunchKernelGGL(mi_epi_pick_kernel<false>, pick_grid, dim3(kBlockPick), 0, c->stream, uv, lo, n, n_dev, nd,
+                       unique, ratio, margin, (const double*)sc, xr_out, ok_out, nullptr, nullptr);
+    return me_check_launch(c, "mi_epi_pick_kernel");
   }
-  hipLaunchKernelGGL(mi_epi_pick_kernel, dim3((n + kBlockPick / 64 - 1) / (kBlockPick / 64)), dim3(kBlockPick), 0,
-                     c->stream, uv,
-                     lo, n, n_dev, nd, unique, ratio, margin, (const double*)sc, xr_out, ok_out);
-  return me_check_launch(c, "mi_epi_pick_kernel");
+  int32_t* back = (int32_t*)(sc + (size_t)n * nd);
+  double* disp_f = (double*)(back + 2 * (size_t)n);
+  hipLaunchKernelGGL(mi_epi_pick_kernel<true>, pick_grid, dim3(kBlockPick), 0, c->stream, uv, lo, n, n_dev, nd, unique,
+                     ratio, margin, (const double*)sc, xr_out, ok_out, back, disp_f);
+  ME_TRY(me_check_launch(c, "mi_epi_pick_kernel<lr>"));
+  ME_TRY(epi_score_launch<true>(c, imgL, imgR, width, height, stride, uv, lo, valid, status, n, n_dev, nd, patch, d_max,
+                                margin, tab, sc, back));
+  hipLaunchKernelGGL(mi_epi_back_pick_kernel, pick_grid, dim3(kBlockPick), 0, c->stream, lo, n, n_dev, nd,
+                     (const double*)sc, (const int32_t*)back, (const double*)disp_f, lr_max, ok_out, lr_err);
+  return me_check_launch(c, "mi_epi_back_pick_kernel");
 }
 
 extern "C" int me_mi_epipolar_match(me_ctx* c, const uint8_t* imgL, const uint8_t* imgR, int width, int height,
@@ -975,6 +1098,28 @@ extern "C" int me_mi_epipolar_match_count(me_ctx* c, const uint8_t* imgL, const 
   ME_CHECK(c, n_dev != nullptr, "me_mi_epipolar_match_count: null count");
   return epipolar_launch(c, imgL, imgR, width, height, stride, uv, lo, nullptr, nullptr, n_max, n_dev, nd, patch, d_max,
                          unique, ratio, margin, xr_out, ok_out);
+}
+
+extern "C" int me_mi_epipolar_match_lr(me_ctx* c, const uint8_t* imgL, const uint8_t* imgR, int width, int height,
+                                       int stride, const float* uv, const int32_t* lo, const uint8_t* valid,
+                                       const uint8_t* status, int n, int nd, int patch, int d_max, int unique,
+                                       double ratio, float margin, double lr_max, float* xr_out, uint8_t* ok_out,
+                                       float* lr_err) {
+  me_range range_("me_mi_epipolar_match_lr");
+  return epipolar_launch(c, imgL, imgR, width, height, stride, uv, lo, valid, status, n, nullptr, nd, patch, d_max,
+                         unique, ratio, margin, xr_out, ok_out, true, lr_max, lr_err);
+}
+
+extern "C" int me_mi_epipolar_match_lr_count(me_ctx* c, const uint8_t* imgL, const uint8_t* imgR, int width,
+                                             int height, int stride, const float* uv, const int32_t* lo,
+                                             const int32_t* n_dev, int n_max, int nd, int patch, int d_max, int unique,
+                                             double ratio, float margin, double lr_max, float* xr_out,
+                                             uint8_t* ok_out, float* lr_err) {
+  me_range range_("me_mi_epipolar_match_lr_count");
+  if (!c) return ME_ERR_INVALID;
+  ME_CHECK(c, n_dev != nullptr, "me_mi_epipolar_match_lr_count: null count");
+  return epipolar_launch(c, imgL, imgR, width, height, stride, uv, lo, nullptr, nullptr, n_max, n_dev, nd, patch, d_max,
+                         unique, ratio, margin, xr_out, ok_out, true, lr_max, lr_err);
 }
 
 // Batch launcher.

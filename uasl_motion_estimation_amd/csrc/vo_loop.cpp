@@ -205,6 +205,7 @@ struct me_vo_loop {
   me_ctx* tctx = nullptr;  // front end (KLT, matchers, scale LM)
   bool shared = false;
   me_vo_loop_config cfg{};
+  double match_lr = 0.0;  // > 0: every matcher call takes its _lr form with this bound (me_vo_loop_set_match_lr)
   std::string err;
   double f = 0, cx = 0, cy = 0;
   int nx = 1, ny = 1;
@@ -529,6 +530,24 @@ struct me_vo_loop {
              "me_klt_track");
     return ME_OK;
   }
+  // The loop's matcher calls: the plain entry points, or their left-right forms (me_hip.h A2b) when match_lr > 0
+  int epi_match(const Imgs& im, const float* uv, const int32_t* lo, const uint8_t* valid, const uint8_t* status, int n,
+                int nd, int unique, float* xr, uint8_t* ok) {
+    if (match_lr > 0.0)
+      return me_mi_epipolar_match_lr(tctx, im.L, im.R, cfg.width, cfg.height, cfg.width, uv, lo, valid, status, n, nd,
+                                     kPatch, cfg.d_max, unique, kRatio, (float)kMargin, match_lr, xr, ok, nullptr);
+    return me_mi_epipolar_match(tctx, im.L, im.R, cfg.width, cfg.height, cfg.width, uv, lo, valid, status, n, nd,
+                                kPatch, cfg.d_max, unique, kRatio, (float)kMargin, xr, ok);
+  }
+  int epi_match_count(const Imgs& im, const float* uv, const int32_t* lo, const int32_t* n_dev, int n_max, int nd,
+                      float* xr, uint8_t* ok) {
+    if (match_lr > 0.0)
+      return me_mi_epipolar_match_lr_count(tctx, im.L, im.R, cfg.width, cfg.height, cfg.width, uv, lo, n_dev, n_max,
+                                           nd, kPatch, cfg.d_max, 1, kRatio, (float)kMargin, match_lr, xr, ok,
+                                           nullptr);
+    return me_mi_epipolar_match_count(tctx, im.L, im.R, cfg.width, cfg.height, cfg.width, uv, lo, n_dev, n_max, nd,
+                                      kPatch, cfg.d_max, 1, kRatio, (float)kMargin, xr, ok);
+  }
   // GPUBackend.klt_match_new: tracked features' matcher, the cells they leave
   // empty, the new features' matcher -- one submission, one round trip
   int klt_match_new(int n, const Imgs& im, const std::vector<int32_t>& lo, const std::vector<uint8_t>& dvalid, int t,
@@ -543,10 +562,8 @@ struct me_vo_loop {
     VL_TRY(me_memcpy_async(tctx, dl, hp, 5 * (size_t)n), "match H2D");
     VL_TRY(dbuf("res", 14 * (size_t)n, &dres), "match");
     uint8_t* r8 = (uint8_t*)dres;
-    VL_TRY(me_mi_epipolar_match(tctx, im.L, im.R, cfg.width, cfg.height, cfg.width, (const float*)dres,
-                                (const int32_t*)dl, (const uint8_t*)dl + 4 * (size_t)n, r8 + 12 * (size_t)n, n, nd,
-                                kPatch, cfg.d_max, 0, kRatio, (float)kMargin, (float*)(r8 + 8 * (size_t)n),
-                                r8 + 13 * (size_t)n),
+    VL_TRY(epi_match(im, (const float*)dres, (const int32_t*)dl, (const uint8_t*)dl + 4 * (size_t)n,
+                     r8 + 12 * (size_t)n, n, nd, 0, (float*)(r8 + 8 * (size_t)n), r8 + 13 * (size_t)n),
            "me_mi_epipolar_match");
     const int m = std::max(cfg.n_feats, 1);
     VL_TRY(dbuf("new", 16 + 17 * (size_t)m, &dn), "match");
@@ -559,10 +576,8 @@ struct me_vo_loop {
                              (float*)(n8 + 16), (int32_t*)(n8 + 16 + 12 * (size_t)m), (int32_t*)n8),
              "me_vo_new_cells");
     }
-    VL_TRY(me_mi_epipolar_match_count(tctx, im.L, im.R, cfg.width, cfg.height, cfg.width, (const float*)(n8 + 16),
-                                      (const int32_t*)(n8 + 16 + 12 * (size_t)m), (const int32_t*)n8, m, nd_new,
-                                      kPatch, cfg.d_max, 1, kRatio, (float)kMargin,
-                                      (float*)(n8 + 16 + 8 * (size_t)m), n8 + 16 + 16 * (size_t)m),
+    VL_TRY(epi_match_count(im, (const float*)(n8 + 16), (const int32_t*)(n8 + 16 + 12 * (size_t)m),
+                           (const int32_t*)n8, m, nd_new, (float*)(n8 + 16 + 8 * (size_t)m), n8 + 16 + 16 * (size_t)m),
            "me_mi_epipolar_match_count");
     const size_t o = 16 * ((14 * (size_t)n + 15) / 16);
     VL_TRY(hbuf("out", o + 16 + 17 * (size_t)m, &ho), "match");
@@ -600,10 +615,8 @@ struct me_vo_loop {
     VL_TRY(dbuf("new", 16 + 17 * (size_t)m, &dn), "match");
     uint8_t* n8 = (uint8_t*)dn;
     VL_TRY(new_corners(im, nullptr, nullptr, nullptr, 0, n8), "me_vo_new_corners");
-    VL_TRY(me_mi_epipolar_match_count(tctx, im.L, im.R, cfg.width, cfg.height, cfg.width, (const float*)(n8 + 16),
-                                      (const int32_t*)(n8 + 16 + 12 * (size_t)m), (const int32_t*)n8, m, nd_new,
-                                      kPatch, cfg.d_max, 1, kRatio, (float)kMargin,
-                                      (float*)(n8 + 16 + 8 * (size_t)m), n8 + 16 + 16 * (size_t)m),
+    VL_TRY(epi_match_count(im, (const float*)(n8 + 16), (const int32_t*)(n8 + 16 + 12 * (size_t)m),
+                           (const int32_t*)n8, m, nd_new, (float*)(n8 + 16 + 8 * (size_t)m), n8 + 16 + 16 * (size_t)m),
            "me_mi_epipolar_match_count");
     VL_TRY(hbuf("out", 16 + 17 * (size_t)m, &ho), "match");
     VL_TRY(me_memcpy_async(tctx, ho, dn, 16 + 17 * (size_t)m), "match D2H");
@@ -631,9 +644,8 @@ struct me_vo_loop {
     VL_TRY(dbuf("m", 17 * (size_t)n, &d), "match");
     VL_TRY(me_memcpy_async(tctx, d, hp, 12 * (size_t)n), "match H2D");
     uint8_t* d8 = (uint8_t*)d;
-    VL_TRY(me_mi_epipolar_match(tctx, im.L, im.R, cfg.width, cfg.height, cfg.width, (const float*)d,
-                                (const int32_t*)(d8 + 8 * (size_t)n), nullptr, nullptr, n, nd, kPatch, cfg.d_max, 1,
-                                kRatio, (float)kMargin, (float*)(d8 + 12 * (size_t)n), d8 + 16 * (size_t)n),
+    VL_TRY(epi_match(im, (const float*)d, (const int32_t*)(d8 + 8 * (size_t)n), nullptr, nullptr, n, nd, 1,
+                     (float*)(d8 + 12 * (size_t)n), d8 + 16 * (size_t)n),
            "me_mi_epipolar_match");
     VL_TRY(hbuf("m_out", 5 * (size_t)n, &ho), "match");
     VL_TRY(me_memcpy_async(tctx, ho, d8 + 12 * (size_t)n, 5 * (size_t)n), "match D2H");
@@ -1324,6 +1336,20 @@ void me_vo_loop_destroy(me_vo_loop* v) {
 }
 
 const char* me_vo_loop_last_error(const me_vo_loop* v) { return v ? v->err.c_str() : "null loop"; }
+
+int me_vo_loop_set_match_lr(me_vo_loop* v, double lr_max) {
+  if (!v) return ME_ERR_INVALID;
+  if (!(lr_max >= 0.0)) {  // (false for NaN)
+    v->err = "me_vo_loop_set_match_lr: match_lr_max must be >= 0 (0: no left-right check)";
+    return ME_ERR_INVALID;
+  }
+  if (v->has_prev || v->failed) {
+    v->err = "me_vo_loop_set_match_lr: match_lr_max is set before the first me_vo_loop_process";
+    return ME_ERR_STATE;
+  }
+  v->match_lr = lr_max;
+  return ME_OK;
+}
 
 int me_vo_loop_process(me_vo_loop* v, int t, const uint8_t* left, const uint8_t* right, me_mem mem) {
   if (!v || !left || !right) return ME_ERR_INVALID;

@@ -125,12 +125,15 @@ class PipelineConfig:
     corner_win: int = 21
     corner_min_eig: float = 1e-4
     klt_fb_max: float = 0.0       # > 0: forward-backward check of the tracker, bound in pixels (klt_fb_host); 0: off
+    match_lr_max: float = 0.0     # > 0: left-right check of the stereo matches, bound in pixels (match_lr_host); 0: off
 
     def __post_init__(self):
         if self.detector not in DETECTORS:
             raise ValueError(f"detector must be one of {DETECTORS}")
         if not self.klt_fb_max >= 0.0:  # (false for NaN)
             raise ValueError("klt_fb_max must be >= 0 (0: no forward-backward check)")
+        if not self.match_lr_max >= 0.0:  # (false for NaN)
+            raise ValueError("match_lr_max must be >= 0 (0: no left-right check)")
 
     @staticmethod
     def from_config(c: int, **kw) -> "PipelineConfig":
@@ -208,6 +211,85 @@ def _pick(uv, d, sc, nd, unique, ratio):
     return xr_f, ok
 
 
+def _pick_kd(d, sc, nd, unique, ratio):
+    """_pick without its last two steps (x_r and the margin test), for the
+    left-right check: (ok, kk, disp) -- the clamped pick index and the FP64
+    disparity d[kk] + delta, the same expressions in the same order."""
+    rows = np.arange(len(sc))
+    k = np.argmax(sc, axis=1)
+    best = sc[rows, k]
+    ok = (k > 0) & (k < nd - 1) & np.isfinite(best)
+    kk = np.clip(k, 1, nd - 2)
+    s_m, s_0, s_p = sc[rows, kk - 1], sc[rows, kk], sc[rows, kk + 1]
+    den = s_m - 2 * s_0 + s_p
+    ok &= np.isfinite(s_m) & np.isfinite(s_p) & (den < 0)
+    if unique:  # uniqueness against the best candidate outside +-2 px
+        m = sc.copy()
+        for j in range(-2, 3):
+            m[rows, np.clip(k + j, 0, nd - 1)] = -np.inf
+        second = m.max(axis=1)
+        ok &= best >= ratio * second
+    den_s = np.where(ok, den, -1.0)
+    delta = np.where(ok, 0.5 * (s_m - s_p) / den_s, 0.0)
+    return ok, kk, d[rows, kk].astype(np.float64) + delta
+
+
+def match_lr_host(be, imgs, uv, lo, nd, dvalid, unique: bool, d_max: int, lr_max: float, ratio: float = 1.2,
+                  patch: int = PATCH):
+    """match_host with the left-right consistency check, the numpy restatement
+    of me_mi_epipolar_match_lr (include/me_hip.h A2b): the forward match, then
+    the right patch that won matched back into the left image over the same
+    disparity candidates; a match is kept iff both passes picked and their FP64
+    disparities differ by at most lr_max.  Returns (xr float32, ok, lr_err
+    float32 (inf where a pass failed), ok_f, ok_b); xr and ok_f are
+    match_host's.  Scores go through be.mi_scores (patch x patch pairs)."""
+    if not lr_max > 0.0:  # (false for NaN)
+        raise ValueError("lr_max must be > 0")
+    n = len(uv)
+    if n == 0:
+        z = np.zeros(0, bool)
+        return np.zeros(0, np.float32), z, np.zeros(0, np.float32), z.copy(), z.copy()
+    half = patch // 2
+    lo = np.asarray(lo, np.int64)
+    x0 = np.floor(uv[:, 0].astype(np.float64) - half).astype(np.int64)  # Rect(x - w, ..) truncation
+    y0 = np.floor(uv[:, 1].astype(np.float64) - half).astype(np.int64)
+    d = lo[:, None] + np.arange(nd, dtype=np.int64)[None, :]
+    H, W = imgs[2][:2]
+    inside = (x0 >= 0) & (y0 >= 0) & (x0 + patch <= W) & (y0 + patch <= H)
+    y0c = np.where(inside, y0, 0)
+    yy = np.repeat(y0c, nd)
+
+    def scores(xl, xr, valid):  # MI of (left patch at xl, right patch at xr), -inf where not scored
+        xyL = np.stack([np.where(valid, xl, 0).ravel(), yy], -1)
+        xyR = np.stack([np.where(valid, xr, 0).ravel(), yy], -1)
+        sc = be.mi_scores(imgs, xyL, xyR).reshape(n, nd).astype(np.float64)
+        return np.where(valid, sc, -np.inf)
+
+    # 1. forward: match_host
+    xr = x0[:, None] - d
+    valid = (xr >= 0) & (d <= d_max) & inside[:, None]
+    if dvalid is not None:
+        valid &= np.asarray(dvalid, bool)[:, None]
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):  # -inf candidates
+        ok_f, kk, disp_f = _pick_kd(d, scores(np.broadcast_to(x0[:, None], d.shape), xr, valid), nd, unique, ratio)
+        xr_f = (uv[:, 0].astype(np.float64) - disp_f).astype(np.float32)
+        ok_f = ok_f & (xr_f >= MARGIN)
+        # 2. backward: the winner's right patch against the left patches d_c to its right
+        xb = x0 - (lo + kk)
+        xl = xb[:, None] + d
+        valid_b = ok_f[:, None] & (d <= d_max) & (xl >= 0) & (xl + patch <= W)
+        valid_b &= ((xb >= 0) & (xb + patch <= W))[:, None]  # (the template inside its row: implied for lo + kk >= 0)
+        # 3. its pick: the forward rule, no uniqueness, no margin test
+        ok_b, _, disp_b = _pick_kd(d, scores(xl, np.broadcast_to(xb[:, None], d.shape), valid_b), nd, False, ratio)
+        ok_b = ok_b & ok_f
+        # 4. the gate
+        a = np.abs(disp_b - disp_f)
+        both = ok_f & ok_b
+        ok = both & (a <= np.float64(lr_max))
+        lr_err = np.where(both, a, np.inf).astype(np.float32)
+    return xr_f, ok, lr_err, ok_f, ok_b
+
+
 def klt_fb_host(klt, prev, cur, pts, fb_max: float):
     """Forward-backward check around any tracker klt(prev, cur, pts) ->
     (pts_out, status): the numpy restatement of me_klt_track_fb
@@ -270,6 +352,7 @@ class Backend:
     d_max = 128
     detector = ("grid", 21, 1e-4)  # (detector, corner_win, corner_min_eig) of the loop's configuration
     klt_fb_max = 0.0  # PipelineConfig.klt_fb_max of the loop's configuration (0: no forward-backward check)
+    match_lr_max = 0.0  # PipelineConfig.match_lr_max of the loop's configuration (0: no left-right check)
 
     def frame_images(self, t: int, left: np.ndarray, right: np.ndarray):
         raise NotImplementedError
@@ -320,12 +403,17 @@ class Backend:
         keep = (st == 1) & in_margin(uv, W, H)
         xr = np.zeros(len(uv), np.float32)
         ok = np.zeros(len(uv), bool)
-        xk, okk = match_host(self, imgs, uv[keep], lo[keep], nd, dvalid[keep], False, self.d_max)
+        xk, okk = self._match(imgs, uv[keep], lo[keep], nd, dvalid[keep], False)
         xr[keep], ok[keep] = xk, okk
         return uv, st, xr, ok
 
+    def _match(self, imgs, uv, lo, nd, dvalid, unique):
+        if self.match_lr_max > 0.0:
+            return match_lr_host(self, imgs, uv, lo, nd, dvalid, unique, self.d_max, self.match_lr_max)[:2]
+        return match_host(self, imgs, uv, lo, nd, dvalid, unique, self.d_max)
+
     def match(self, imgs, uv, lo, nd, unique):
-        return match_host(self, imgs, uv, lo, nd, None, unique, self.d_max)
+        return self._match(imgs, uv, lo, nd, None, unique)
 
     def klt_match_new(self, h, imgs, lo, nd, dvalid, t, grid, d_min, nd_new):
         """klt_match, then the new features of the cells the good tracked
@@ -632,6 +720,13 @@ class GPUBackend(Backend):
         H, W = imgs[2]
         c = self.mctx
         V = ctypes.c_void_p
+        if self.match_lr_max > 0.0:
+            c.check(c.lib.me_mi_epipolar_match_lr(c.h, V(imgs[0]), V(imgs[1]), W, H, W, V(d_uv), V(d_lo),
+                                                  V(d_valid) if d_valid else None, V(d_status) if d_status else None,
+                                                  n, nd, PATCH, self.d_max, 1 if unique else 0, 1.2, float(MARGIN),
+                                                  float(self.match_lr_max), V(d_xr), V(d_ok), None),
+                    "me_mi_epipolar_match_lr")
+            return
         c.check(c.lib.me_mi_epipolar_match(c.h, V(imgs[0]), V(imgs[1]), W, H, W, V(d_uv), V(d_lo),
                                            V(d_valid) if d_valid else None, V(d_status) if d_status else None, n, nd,
                                            PATCH, self.d_max, 1 if unique else 0, 1.2, float(MARGIN), V(d_xr),
@@ -693,10 +788,17 @@ class GPUBackend(Backend):
                                           nx, ny, float(cw), float(ch), nf, t, d_min, V(dn + 16),
                                           V(dn + 16 + 12 * m), V(dn)),
                     "me_vo_new_cells")
-        c.check(c.lib.me_mi_epipolar_match_count(c.h, V(imgs[0]), V(imgs[1]), W, H, W, V(dn + 16), V(dn + 16 + 12 * m),
-                                                 V(dn), m, nd_new, PATCH, self.d_max, 1, 1.2, float(MARGIN),
-                                                 V(dn + 16 + 8 * m), V(dn + 16 + 16 * m)),
-                "me_mi_epipolar_match_count")
+        if self.match_lr_max > 0.0:
+            c.check(c.lib.me_mi_epipolar_match_lr_count(c.h, V(imgs[0]), V(imgs[1]), W, H, W, V(dn + 16),
+                                                        V(dn + 16 + 12 * m), V(dn), m, nd_new, PATCH, self.d_max, 1,
+                                                        1.2, float(MARGIN), float(self.match_lr_max),
+                                                        V(dn + 16 + 8 * m), V(dn + 16 + 16 * m), None),
+                    "me_mi_epipolar_match_lr_count")
+        else:
+            c.check(c.lib.me_mi_epipolar_match_count(c.h, V(imgs[0]), V(imgs[1]), W, H, W, V(dn + 16),
+                                                     V(dn + 16 + 12 * m), V(dn), m, nd_new, PATCH, self.d_max, 1, 1.2,
+                                                     float(MARGIN), V(dn + 16 + 8 * m), V(dn + 16 + 16 * m)),
+                    "me_mi_epipolar_match_count")
         o = 16 * ((14 * n + 15) // 16)
         ho = self._hbuf("out", o + 16 + 17 * m)
         c.copy_async(ho, dres, 14 * n)
@@ -1034,6 +1136,7 @@ class WindowedStereoVO:
         self.be.d_max = cfg.d_max
         self.be.detector = (cfg.detector, cfg.corner_win, cfg.corner_min_eig)
         self.be.klt_fb_max = float(cfg.klt_fb_max)
+        self.be.match_lr_max = float(cfg.match_lr_max)
         if hasattr(backend, "reserve"):
             backend.reserve(cfg)
         self.K = np.asarray(S.intrinsics(cfg.width, cfg.height) if K is None else K, np.float64)
@@ -1543,6 +1646,12 @@ class NativeStereoVO:
         self.ctx.check(self.lib.me_vo_loop_create(self.ctx.h, self.tctx.h, ctypes.byref(c), ctypes.byref(h)),
                        "me_vo_loop_create")
         self.h = h
+        # (a setter, not a configuration field: me_vo_loop_config keeps its layout)
+        try:
+            self._check(self.lib.me_vo_loop_set_match_lr(self.h, float(cfg.match_lr_max)), "me_vo_loop_set_match_lr")
+        except Exception:
+            self.close()  # (the loop exists: destroy it, give the contexts their CUs back)
+            raise
         self.log_events = log_events
         self._keep = {}  # device images of the last two keyframes (the loop reads them until process(t + 1))
 
