@@ -266,30 +266,46 @@ def cmd_scale_ts(a):
 
 
 def cmd_cam_ts(a):
-    """Camera (0, 0)'s assembly workgroup phases (a -DME_CAM_TS=1 build): the
-    slot loop (loads + residual/Jacobian + sums), block_sum<27>, partial stores +
-    arrival, and (when last) the camera reduce; s_memtime ticks per execution."""
+    """One camera-assembly unit's workgroup phases (a -DME_CAM_TS=1 build): the
+    slot pass (loads + residual/Jacobian + sums), block_sum<27>, partial stores +
+    arrival, and (when last) the camera reduce; s_memtime ticks per execution.
+    Reported for unit 0 (the first variable camera's first 256 slots: the
+    lightest camera of a sliding window) and for the first unit of the heaviest
+    camera (a full unit whose camera has the most partials to reduce)."""
     from uasl_motion_estimation_amd.optimisation import DeviceBAProblem, SolverOptions
     ctx = _setup(a.lib)
     fn = ctx.lib.me_cam_ts
     fn.argtypes = [ctypes.POINTER(ctypes.c_longlong), ctypes.c_int]
     buf = (ctypes.c_longlong * 8)()
-    d = DeviceBAProblem(_ba_problem(a.config), ctx)
+    bp = _ba_problem(a.config)
+    counts = np.bincount(bp.cam_idx, minlength=len(bp.cams))[bp.fixed_frames:]
+    units = np.maximum(1, -(-counts // 256))
+    heavy = int(np.argmax(counts))
+    first = np.concatenate([[0], np.cumsum(units)])
+    d = DeviceBAProblem(bp, ctx)
     o = SolverOptions.fixed_iterations(10)
-    for _ in range(3):
-        d.reset()
-        d.solve(o)
-    ctx.synchronize()
-    fn(buf, 1)
-    for _ in range(20):
-        d.reset()
-        d.solve(o)
-    ctx.synchronize()
-    fn(buf, 0)
-    n = max(buf[0], 1)
-    print(json.dumps({"executions": buf[0], "slot_loop": round(buf[1] / n), "block_sum27": round(buf[2] / n),
-                      "store_arrive": round(buf[3] / n), "times_last": buf[5],
-                      "reduce_when_last": round(buf[4] / max(buf[5], 1))}))
+    out = {"camera_counts": counts.tolist(), "units": int(units.sum())}
+    set_unit = getattr(ctx.lib, "me_cam_ts_unit", None)  # (a build from before the unit table stamps camera (0, 0) only)
+    for tag, unit in (("unit0", 0), (f"heaviest_camera{heavy}_unit{int(first[heavy])}", int(first[heavy]))):
+        if set_unit is None and unit:
+            break
+        if set_unit is not None and set_unit(unit) != 0:
+            sys.exit("me_cam_ts_unit failed")
+        for _ in range(3):
+            d.reset()
+            d.solve(o)
+        ctx.synchronize()
+        fn(buf, 1)
+        for _ in range(20):
+            d.reset()
+            d.solve(o)
+        ctx.synchronize()
+        fn(buf, 0)
+        n = max(buf[0], 1)
+        out[tag] = {"executions": buf[0], "slot_pass": round(buf[1] / n), "block_sum27": round(buf[2] / n),
+                    "store_arrive": round(buf[3] / n), "times_last": buf[5],
+                    "reduce_when_last": round(buf[4] / max(buf[5], 1))}
+    print(json.dumps(out))
 
 
 def cmd_step_ts(a):

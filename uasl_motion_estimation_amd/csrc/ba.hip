@@ -335,9 +335,9 @@ __global__ __launch_bounds__(BLK) void linearize_kernel(Geo g, Bufs b) {
 }
 
 // Unscaled U = Jc^T Jc (21 unique) and g = Jc^T r per variable camera, in
-// two deterministic stages (cam_assemble_body): workgroup (c, k) sums chunks
-// k, k + ck, ... of 256 slots of camera c into a partial; cam_reduce adds
-// the ck partials in order.
+// two deterministic stages (cam_assemble_body): a workgroup sums one unit
+// (256 slots of one camera, the plan's unit table) into a partial; cam_reduce
+// adds the camera's partials in unit order.
 // The last workgroup to arrive on a counter, with a written-through hand-off
 // (the form of the camera solve's workers): thread 0 stored the workgroup's
 // partials with sc1 stores, drains them before a relaxed arrival, and the last
@@ -356,18 +356,19 @@ __device__ __forceinline__ bool last_arrival_wt(unsigned* cnt, unsigned expected
   return slast != 0;
 }
 
-// Camera ci: lane u < 27 sums component u of the ck partials (fixed order)
+// Camera ci: lane u < 27 sums component u of the camera's partials, units
+// first .. first + count - 1 (fixed order)
 // -> raw U, column norms, raw gradient; unless sharded, the Jacobi scaling
 // (iteration 0) and the scaled blocks.  Called by every thread of a block.
 __device__ void cam_reduce_body(const Geo& g, const Bufs& b, int sharded, const double* cpart, double* colnorm,
-                                double* gc_raw, double* Uraw, int ci) {
+                                double* gc_raw, double* Uraw, int ci, int first, int count) {
   __shared__ double tot[27];
   __shared__ double csl[6];
   const State* st = b.st;
   const int u = threadIdx.x;
   if (u < 27) {
     double sum = 0.0;
-    for (int k = 0; k < g.ck; ++k) sum += a_ld<true>(&cpart[27 * ((long)ci * g.ck + k) + u]);  // (written through)
+    for (int k = 0; k < count; ++k) sum += a_ld<true>(&cpart[27 * ((long)first + k) + u]);  // (written through)
     tot[u] = sum;
     if (u < 21) Uraw[21 * (long)ci + u] = sum;
     else gc_raw[6 * ci + u - 21] = sum;
@@ -403,16 +404,20 @@ __device__ void cam_reduce_body(const Geo& g, const Bufs& b, int sharded, const 
 // Unscaled U = Jc^T Jc (21 unique) and g = Jc^T r per variable camera, in
 // two deterministic stages over the camera's observations in c_obs slot
 // order (each piece formed here from the observation's residual and
-// Jacobian): workgroup (c, k) sums chunks k, k + ck, ... of 256 slots of
-// camera c into a partial; the last of the ck
-// workgroups of camera c to finish adds the ck partials in order.
+// Jacobian): the workgroup of unit un sums the unit's slots (at most 256,
+// one per thread) into a partial; the last of a camera's workgroups to
+// finish adds the camera's partials in unit order.  Every workgroup makes
+// one pass whatever its camera's share of the observations (a sliding
+// window's newest cameras see five times the oldest's), and a unit past the
+// plan's unit total (the host launches a bound) returns at once.
 // Threads 0 .. kBlock-1 of the block take part (in a wider block the other
 // waves have exited: barriers count only live waves).
-#ifdef ME_CAM_TS  // timing experiment only: phase split of camera (0, 0)'s assembly workgroup, s_memtime ticks
+#ifdef ME_CAM_TS  // timing experiment only: phase split of one unit's assembly workgroup (me_cam_ts_unit; 0 = camera 0's first), s_memtime ticks
 __device__ unsigned long long g_cam_ts[8];
+__device__ int g_cam_ts_unit;
 #define CAM_T(i)                                                                           \
   do {                                                                                     \
-    if (ci == 0 && k == 0 && threadIdx.x == 0) {                                           \
+    if (un == g_cam_ts_unit && threadIdx.x == 0) {                                         \
       const long long t_ = (long long)__builtin_amdgcn_s_memtime();                        \
       if ((i) > 0) atomicAdd(&g_cam_ts[(i)], (unsigned long long)(t_ - cam_prev_));        \
       else atomicAdd(&g_cam_ts[0], 1ull);                                                  \
@@ -426,19 +431,24 @@ __device__ unsigned long long g_cam_ts[8];
 #endif
 template <int OD>
 __device__ __forceinline__ void cam_assemble_body(const Geo& g, const Bufs& b, double* cpart, int sharded,
-                                                  double* colnorm, double* gc_raw, double* Uraw, int ci, int k) {
+                                                  double* colnorm, double* gc_raw, double* Uraw, int un) {
   __shared__ double rows[kBlock / 16 * 27];
   const State* st = b.st;
+  // (the unit's entry is requested beside the state words: one round)
+  const int4 ue = *(const int4*)(b.cunit + (long)kCuStride * un);  // camera, slot range, the camera's unit count
+  const int ufirst = b.cunit[(long)kCuStride * un + CU_FIRST];
   if (st->done || !st->need_lin) return;
+  const int ci = ue.x;
+  if (ci < 0) return;  // past the plan's unit total
 #ifdef ME_CAM_TS
   long long cam_prev_ = 0;
 #endif
   CAM_T(0);
-  const int beg = b.c_off[ci], end = b.c_off[ci + 1];
   double v[27];
   for (int i = 0; i < 27; ++i) v[i] = 0;
   const int cur = st->cur;
-  for (int q = beg + k * kBlock + threadIdx.x; q < end; q += g.ck * kBlock) {
+  const int q = ue.y + threadIdx.x;
+  if (q < ue.z) {
     // the observation's residual and Jacobian at the linearisation point, as
     // linearize_kernel forms them (same function, same Huber scaling: the same
     // pieces bit for bit), then Jc^T Jc (21) and Jc^T r (6)
@@ -479,26 +489,27 @@ __device__ __forceinline__ void cam_assemble_body(const Geo& g, const Bufs& b, d
     double sum = 0.0;
 #pragma unroll
     for (int r = 0; r < kBlock / 16; ++r) sum += rows[r * 27 + threadIdx.x];
-    a_st<true>(&cpart[27 * ((long)ci * g.ck + k) + threadIdx.x], sum);  // (lanes of wave 0: its vmcnt drain covers them)
+    a_st<true>(&cpart[27 * (long)un + threadIdx.x], sum);  // (lanes of wave 0: its vmcnt drain covers them)
   }
-  const bool last = last_arrival_wt(b.cnt + ci, g.ck);
+  const bool last = last_arrival_wt(b.cnt + ci, (unsigned)ue.w);
   CAM_T(3);
   if (!last) return;
-  cam_reduce_body(g, b, sharded, cpart, colnorm, gc_raw, Uraw, ci);
+  cam_reduce_body(g, b, sharded, cpart, colnorm, gc_raw, Uraw, ci, ufirst, ue.w);
   CAM_T(4);
 #ifdef ME_CAM_TS
-  if (ci == 0 && k == 0 && threadIdx.x == 0) atomicAdd(&g_cam_ts[5], 1ull);
+  if (un == g_cam_ts_unit && threadIdx.x == 0) atomicAdd(&g_cam_ts[5], 1ull);
 #endif
 }
 
+// grid: g.ncu units (the host's bound on the plan's unit total)
 __global__ __launch_bounds__(kBlock) void cam_assemble_kernel(Geo g, Bufs b, double* cpart, int sharded,
                                                               double* colnorm, double* gc_raw, double* Uraw) {
   // (one instance per model: the mono model's row selection would otherwise
   // keep the stereo path's Jacobian arrays out of registers)
   if (g.od == 4)
-    cam_assemble_body<4>(g, b, cpart, sharded, colnorm, gc_raw, Uraw, blockIdx.x, blockIdx.y);
+    cam_assemble_body<4>(g, b, cpart, sharded, colnorm, gc_raw, Uraw, blockIdx.x);
   else
-    cam_assemble_body<2>(g, b, cpart, sharded, colnorm, gc_raw, Uraw, blockIdx.x, blockIdx.y);
+    cam_assemble_body<2>(g, b, cpart, sharded, colnorm, gc_raw, Uraw, blockIdx.x);
 }
 
 // Camera assembly riding in the Schur launch (iterations after the first,
@@ -506,7 +517,7 @@ __global__ __launch_bounds__(kBlock) void cam_assemble_kernel(Geo g, Bufs b, dou
 struct CamArgs {
   double *cpart, *colnorm, *gc_raw, *Uraw;
   int on;
-  int ncam;  // leading workgroups of the launch that assemble cameras (m ck, padded to whole rounds of 8 XCDs)
+  int ncam;  // leading workgroups of the launch that assemble cameras (g.ncu units, padded to whole rounds of 8 XCDs)
 };
 
 // Sharded mode, first linearisation: the rank's input flags (bad index,
@@ -664,11 +675,14 @@ __global__ __launch_bounds__(BLK) void pt_schur_kernel(Geo g, Bufs b, Opts o, Ca
   if (ca.on && (int)blockIdx.x < ca.ncam) {
     if (threadIdx.x >= kBlock) return;
     const int q = blockIdx.x;
-    if (q >= g.m * g.ck) return;  // (padding to a multiple of 8)
+    if (q >= g.ncu) return;  // (padding to a multiple of 8)
+#ifdef ME_EXP_NOCAM  // timing experiment only (wrong results): the launch without its camera work, DESIGN §5.4's yardstick
+    return;
+#endif
     if (g.od == 4)
-      cam_assemble_body<4>(g, b, ca.cpart, 0, ca.colnorm, ca.gc_raw, ca.Uraw, q / g.ck, q % g.ck);
+      cam_assemble_body<4>(g, b, ca.cpart, 0, ca.colnorm, ca.gc_raw, ca.Uraw, q);
     else
-      cam_assemble_body<2>(g, b, ca.cpart, 0, ca.colnorm, ca.gc_raw, ca.Uraw, q / g.ck, q % g.ck);
+      cam_assemble_body<2>(g, b, ca.cpart, 0, ca.colnorm, ca.gc_raw, ca.Uraw, q);
     return;
   }
   const int sblk = (int)blockIdx.x - (ca.on ? ca.ncam : 0);  // this workgroup's index among the Schur runs
@@ -2543,13 +2557,14 @@ __global__ __launch_bounds__(kStepBlock) void pt_step_kernel(Geo g, Bufs b, Opts
   const int j = blockIdx.x * kStepPts + (threadIdx.x / kStepG);
   double mc = 0, cc = 0, s2 = 0, xn2 = 0;
   if (j < g.np && !st->fail) {  // uniform within a 16-lane group
-    // Every load of the point and of this lane's first CSR slot is requested
-    // in three dependent rounds (point data + offsets | slot: camera, obs
-    // index, W | camera step / scales, observation, candidate camera) before
-    // any arithmetic; further slots (points with more than 16 observations)
-    // load in the loops.  The slot's camera is p_cam + nf (plan_segsort_kernel
-    // writes p_cam[q] = cam_idx[p_obs[q]] - nf), so the candidate camera does
-    // not wait for a cam_idx read.
+    // Every load of the point and of this lane's first CSR slot, and the
+    // second slot's but W, is requested in three dependent rounds (point data
+    // + offsets | slot: camera, obs index, W | camera step / scales,
+    // observation, candidate camera) before any arithmetic; further slots
+    // (points with more than 32 observations) load in the loops.  The slot's
+    // camera is p_cam + nf (plan_segsort_kernel writes p_cam[q] =
+    // cam_idx[p_obs[q]] - nf), so the candidate camera does not wait for a
+    // cam_idx read.
     const int cur = st->cur;
     const double* Wo = b.Wo;
     double psv[3], gpv[3], Lv[9], xv[3], Vv[9];
@@ -2572,6 +2587,18 @@ __global__ __launch_bounds__(kStepBlock) void pt_step_kernel(Geo g, Bufs b, Opts
       o0 = b.p_obs[q0];
       for (int i = 0; i < 18; ++i) W0[i] = Wo[18 * (long)q0 + i];  // (unused for a fixed camera)
     }
+    // the lane's second slot (tracks of 17 .. 32 observations: 13.5 % of the
+    // config-3 window's, in 93 % of its workgroups) is requested in the same
+    // rounds, all but its W: loop (3)'s second pass waits for no load of its
+    // own and loop (1)'s only for W, already addressed.  (W too costs 36
+    // registers and the second wave per SIMD: config 4 +2.7 us)
+    const int q1 = q0 + kStepG;
+    const bool has1 = q1 < end;
+    int ci1 = -1, o1 = 0;
+    if (has1) {
+      ci1 = b.p_cam[q1];
+      o1 = b.p_obs[q1];
+    }
     // candidate cameras x + D_c y_c formed here from the current ones (the
     // camera workgroup stores the same values, cam_cand; not read back)
     const double* cams_x = b.cams[cur];
@@ -2584,23 +2611,40 @@ __global__ __launch_bounds__(kStepBlock) void pt_step_kernel(Geo g, Bufs b, Opts
       for (int k = 0; k < OD; ++k) f0[k] = b.obs[(long)OD * o0 + k];
       if (OD == 2) right0 = b.cam_id[o0] != 0;
     }
-    double cv0[6];
+    double ys1[6], f1[4];
+    int cam1 = 0, right1 = 0;
+    if (has1) {
+      if (ci1 >= 0)
+        for (int a = 0; a < 6; ++a) ys1[a] = b.csc[6 * ci1 + a] * b.yc[6 * ci1 + a];
+      cam1 = ci1 + g.nf;
+      for (int k = 0; k < OD; ++k) f1[k] = b.obs[(long)OD * o1 + k];
+      if (OD == 2) right1 = b.cam_id[o1] != 0;
+    }
+    double cv0[6], cv1[6];
     if (has0)
       for (int a = 0; a < 6; ++a) {
         const double xa = cams_x[6 * cam0 + a];
         cv0[a] = ci0 >= 0 ? cam_cand(xa, ys0[a]) : xa;
       }
+    if (has1)
+      for (int a = 0; a < 6; ++a) {
+        const double xa = cams_x[6 * cam1 + a];
+        cv1[a] = ci1 >= 0 ? cam_cand(xa, ys1[a]) : xa;
+      }
     STEP_T(1);  // (the first round of loads issued; returns at first use below)
     // (1) sum over the point's slots of W_q^T (Dc y_c)
     double t[3] = {0.0, 0.0, 0.0};
     for (int q = q0; q < end; q += kStepG) {
-      const bool first = q == q0;
-      const int ci = first ? ci0 : b.p_cam[q];
+      const bool first = q == q0, second = q == q1;
+      const int ci = first ? ci0 : second ? ci1 : b.p_cam[q];
       if (ci < 0) continue;
       double ys[6], W[18];
       if (first) {
         for (int a = 0; a < 6; ++a) ys[a] = ys0[a];
         for (int i = 0; i < 18; ++i) W[i] = W0[i];
+      } else if (second) {
+        for (int a = 0; a < 6; ++a) ys[a] = ys1[a];
+        for (int i = 0; i < 18; ++i) W[i] = Wo[18 * (long)q + i];
       } else {
         for (int a = 0; a < 6; ++a) ys[a] = b.csc[6 * ci + a] * b.yc[6 * ci + a];
         for (int i = 0; i < 18; ++i) W[i] = Wo[18 * (long)q + i];
@@ -2643,13 +2687,17 @@ __global__ __launch_bounds__(kStepBlock) void pt_step_kernel(Geo g, Bufs b, Opts
     STEP_T(3);  // point solve, candidate point
     // (3) candidate cost of the point's observations
     for (int q = q0; q < end; q += kStepG) {
-      const bool first = q == q0;
+      const bool first = q == q0, second = q == q1;
       double cv[6], f[4];
       int right = 0;
       if (first) {
         for (int a = 0; a < 6; ++a) cv[a] = cv0[a];
         for (int k = 0; k < OD; ++k) f[k] = f0[k];
         right = right0;
+      } else if (second) {
+        for (int a = 0; a < 6; ++a) cv[a] = cv1[a];
+        for (int k = 0; k < OD; ++k) f[k] = f1[k];
+        right = right1;
       } else {
         const int o = b.p_obs[q];
         const int ci = b.p_cam[q], cam = ci + g.nf;
@@ -2919,21 +2967,40 @@ __global__ __launch_bounds__(kScanBlock) void plan_scan_kernel(Geo g, Bufs b, Op
     if (lane == 63) ctot[c] = cx;
   }
   __syncthreads();
+  __shared__ int ufst[kMaxScanCams + 1];  // first camera-assembly unit of every camera | the unit total
+  __shared__ int ctotal;                  // c_off[m]
   if (t == 0) {
-    int acc = 0;
+    int acc = 0, units = 0;
     for (int c = 0; c < g.m; ++c) {
       b.c_off[c] = acc;
       const int v = ctot[c];
       ctot[c] = acc;
       acc += v;
+      ufst[c] = units;
+      units += max(1, (v + kBlock - 1) / kBlock);
     }
     b.c_off[g.m] = acc;
+    ctotal = acc;
+    ufst[g.m] = units;  // (at most g.ncu = ceil(no / 256) + m: every camera rounds up by less than one unit)
   }
   __syncthreads();
   for (int c = wv; c < g.m; c += kScanBlock / 64) {
     const int k0 = min(g.nblk_obs, lane * bchunk), k1 = min(g.nblk_obs, k0 + bchunk);
     for (int k = k0; k < k1; ++k) w.blk_cam[(long)k * g.nc + g.nf + c] += ctot[c];
+    // the camera's units (ba_kernels.hpp CU_*): 256 slots each, the last one the remainder
+    const int cbeg = ctot[c], cend = c + 1 < g.m ? ctot[c + 1] : ctotal;
+    const int first = ufst[c], count = ufst[c + 1] - first;
+    for (int k = lane; k < count; k += 64) {
+      int* e = b.cunit + (long)kCuStride * (first + k);
+      e[CU_CAM] = c;
+      e[CU_BEG] = cbeg + k * kBlock;
+      e[CU_END] = min(cend, cbeg + (k + 1) * kBlock);
+      e[CU_COUNT] = count;
+      e[CU_FIRST] = first;
+    }
   }
+  // units the host launches beyond the total: no camera
+  for (int u = ufst[g.m] + t; u < (g.ncu + 7) / 8 * 8; u += kScanBlock) b.cunit[(long)kCuStride * u + CU_CAM] = -1;
   for (int i = t; i < g.n6; i += kScanBlock) b.csc[i] = 0.0;
   if (t == 0) {
     State* st = b.st;
@@ -2950,6 +3017,7 @@ __global__ __launch_bounds__(kScanBlock) void plan_scan_kernel(Geo g, Bufs b, Op
     st->x_cost = st->cand_cost = st->model_change = st->initial_cost = 0.0;
     st->cam_step2 = st->cam_xn2 = st->cam_model = st->last_q = 0.0;
     for (int k = 0; k < 16; ++k) st->stamps[k] = 0;
+    st->stamps[14] = ufst[g.m];  // the camera-assembly unit total (me_debug_read; no timing build uses the word)
     if (st->bad_input || st->infeasible) {
       st->done = 1;
       st->termination = 2;
@@ -3183,7 +3251,7 @@ struct Plan {
   double* colnorm = nullptr;
   double* gc_raw = nullptr;
   double* Uraw = nullptr;
-  double* cpart = nullptr;  // camera assembly partials (m x ck x 27)
+  double* cpart = nullptr;  // camera assembly partials (27 per unit)
   double* host = nullptr;  // pinned staging (inputs in, State / results out)
   State* hstate[2] = {nullptr, nullptr};  // pinned slots of the pipelined State polls
   bool dev = false;        // problem arrays are device-resident
@@ -3323,8 +3391,9 @@ int plan_build(me_ctx* c, const me_ba_problem* p, const me_ba_options* opt, Plan
   g.nblk_lin = (int)std::max(1L, rup(std::max(g.no, 1), lin_block(g.no)) / lin_block(g.no));
   g.nblk_pts = (int)std::max(1L, rup(std::max(g.np, 1), kPtBlock) / kPtBlock);
   g.jacobi = opt->jacobi_scaling ? 1 : 0;
-  g.ck = (int)std::min(64L, std::max(1L, rup(std::max(g.no, 1), (long)std::max(g.m, 1) * kBlock) /
-                                             ((long)std::max(g.m, 1) * kBlock)));
+  // camera-assembly units launched: the per-camera counts of a device-resident problem are unknown here, so the
+  // bound on sum max(1, ceil(n_c / 256)); the plan's unit table marks the units past the total
+  g.ncu = (int)(rup(std::max(g.no, 1), kBlock) / kBlock) + g.m;
   g.nblk_step = (int)std::max(1L, rup(std::max(g.np, 1), kStepPts) / kStepPts);
   g.pstride = std::max({g.nblk_obs, g.nblk_lin, g.nblk_pts, g.nblk_step, g.ksplit});
   std::memcpy(g.K0, p->K0, sizeof(g.K0));
@@ -3403,7 +3472,8 @@ int plan_build(me_ctx* c, const me_ba_problem* p, const me_ba_options* opt, Plan
   add(8 * (size_t)(g.n6 + 2), &P.colnorm);  // (+ the sharded first exchange's input flags)
   add(8 * (size_t)g.n6, &P.gc_raw);
   add(8 * 21 * (size_t)std::max(g.m, 1), &P.Uraw);
-  add(8 * 27 * (size_t)std::max(g.m, 1) * g.ck, &P.cpart);
+  add(8 * 27 * (size_t)g.ncu, &P.cpart);
+  add(4 * (size_t)kCuStride * (size_t)rup(g.ncu, 8), &b.cunit);
   add(4 * (size_t)(g.m + 1 + 3 + 2), &b.cnt);  // counters: per camera (cam_assemble) | pt_step | solve sync (2) | fused assembly | roster (2)
   add(4 * (size_t)blocks((long)g.npairs * 256, kSolveBlock / kSaGroups), &b.asm_claim);  // (cleared with cnt)
   const size_t work_bytes = 4 * (2 * (size_t)g.np + (size_t)g.nblk_obs * g.nc + 4);
@@ -3554,7 +3624,7 @@ int enqueue_linearize(Plan& P) {
       hipLaunchKernelGGL((linearize_kernel<2, kBlock>), dim3(g.nblk_lin), dim3(kBlock), 0, s, g, P.b);
   }
   // After the first linearisation the Jacobi scaling is fixed and the Schur
-  // pass no longer needs the camera assembly: its m x ck workgroups then ride
+  // pass no longer needs the camera assembly: its unit workgroups then ride
   // in the Schur launch (one launch fewer per iteration; a second stream with
   // event fork/join measured slower).  Sharded runs too: a rank's U and g
   // blocks are then scaled by the fixed global scaling, and the exchange sums
@@ -3562,9 +3632,9 @@ int enqueue_linearize(Plan& P) {
   const bool first = P.n_enq == 0;
   const bool fused = !first && g.m > 0;
   ++P.n_enq;
-  CamArgs ca{P.cpart, P.colnorm, P.gc_raw, P.Uraw, fused ? 1 : 0, fused ? (g.m * g.ck + 7) / 8 * 8 : 0};
+  CamArgs ca{P.cpart, P.colnorm, P.gc_raw, P.Uraw, fused ? 1 : 0, fused ? (g.ncu + 7) / 8 * 8 : 0};
   if (g.m > 0 && !fused)
-    hipLaunchKernelGGL(cam_assemble_kernel, dim3(g.m, g.ck), dim3(kBlock), 0, s, g, P.b, P.cpart, sh ? 1 : 0,
+    hipLaunchKernelGGL(cam_assemble_kernel, dim3(g.ncu), dim3(kBlock), 0, s, g, P.b, P.cpart, sh ? 1 : 0,
                        P.colnorm, P.gc_raw, P.Uraw);
   if (sh && !fused) {
     // the Jacobi scaling needs the global column norms: the first exchange
@@ -4422,6 +4492,11 @@ extern "C" int me_cam_ts(long long* out, int reset) {
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_cam_ts), z, sizeof z) != hipSuccess) return -1;
   }
   return 0;
+}
+// the unit whose workgroup is stamped (index into the plan's unit table)
+extern "C" int me_cam_ts_unit(int unit) {
+  if (unit < 0) return -1;
+  return hipMemcpyToSymbol(HIP_SYMBOL(g_cam_ts_unit), &unit, sizeof unit) == hipSuccess ? 0 : -1;
 }
 #endif
 

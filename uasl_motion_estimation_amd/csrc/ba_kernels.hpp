@@ -11,7 +11,8 @@
 //                  later stage is shared), HuberLoss(1.0) corrector, cost;
 //                  stores only the normal-equation pieces (J^T J, J^T r
 //                  blocks), never the Jacobian itself.
-//   cam_assemble   ck workgroups per variable camera, the last to finish
+//   cam_assemble   one workgroup per unit of 256 slots of a variable camera
+//                  (the plan's unit table), the last of a camera's to finish
 //                  reduces: Jacobi column norms (iteration 0), scaled
 //                  U = Jc'Jc, g_c = Jc'r.
 //   pt_schur       per landmark sub-chunk: V = Jp'Jp, g_p, V + D/radius ->
@@ -63,7 +64,8 @@ struct State {
   double x_cost, cand_cost, model_change, initial_cost;
   double cam_step2, cam_xn2, cam_model;  // cam_model: -(g_c.y_c + y_c^T U y_c / 2), this rank's camera part
   double last_q;
-  long long stamps[16];  // timing builds only (-DME_SOLVE_TS, -DME_SCHUR_STAMPS): s_memtime phase stamps, me_debug_read
+  long long stamps[16];  // timing builds only (-DME_SOLVE_TS, -DME_SCHUR_STAMPS): s_memtime phase stamps, me_debug_read;
+                         // [14] in every build: the plan's camera-assembly unit total
 };
 
 // Scalars reduced from block partials (one slot per quantity).
@@ -71,7 +73,7 @@ enum { R_COST = 0, R_GMAX_PT, R_MODEL, R_CAND, R_STEP2, R_XN2, R_COUNT };
 
 struct Geo {
   int nc, np, no, nf, m, n6, Rpad, T, Ts, spts, nsub, ksplit, npairs, nblk_obs, nblk_lin, nblk_pts, nblk_step, pstride, jacobi,
-      ck;
+      ncu;                 // camera-assembly units the host launches: the bound ceil(no / 256) + m on the plan's unit total
   // band-sorted Schur pass (plan_band / plan_order): landmark runs of rlen = spts x rsub landmarks in
   // (first tile, last tile) order, each split into sgrp tile groups of stpw tiles (ksplit = nruns x sgrp)
   int nruns, rlen, rsub, sgrp, stpw, nblkp;
@@ -98,6 +100,7 @@ struct Bufs {
   int* c_obs;
   int* tmp_obs;       // plan: unsorted CSR-by-point slots
   int* cpos;          // obs -> slot in c_obs (-1: fixed camera)
+  int* cunit;         // camera-assembly unit table (plan_scan): kCuStride ints per unit, see CU_* below
   double* obsx;       // no * 9  (V_o, g_o unscaled)
   uint8_t* dup;       // obs shares (point, camera) with another obs
   double* Abuf;       // n6 * (n6|1) factorisation workspace (when S does not fit LDS)
@@ -127,13 +130,22 @@ struct Bufs {
   double* scal;       // R_COUNT reduced scalars (all-reduce target in sharded mode)
   State* st;
   int* work;          // plan build: cnt_p[np] | fill_p[np] | blk_cam[nblk_obs*nc] | flags[4] (zeroed)
-  unsigned* cnt;      // last-arrival counters: m (cam_assemble, per camera) + 1 (pt_step); re-armed by the last
+  unsigned* cnt;      // last-arrival counters: m (cam_assemble, per camera: its unit count) + 1 (pt_step); re-armed by the last
   unsigned* ssync;    // camera solve, global-memory form: {step epoch, worker step count} (zeroed by s_assemble)
   unsigned* roster;   // camera solve: the trailing workers' roster (roster.hpp; 2 words, re-zeroed by pt_step)
   unsigned* asm_claim;  // fused assembly: per unit, the generation of the launch whose workgroup claimed it
   double* out;        // State | cams[cur] | pts[cur] for the single read-back
   double* xch;        // sharded only (else null): the packed per-iteration exchange, see xo_* below
 };
+
+// Camera-assembly unit table: a unit is 256 consecutive slots of one variable
+// camera's segment of c_obs; camera c has max(1, ceil(n_c / 256)) units (an
+// empty camera keeps one empty unit, so its U, g and scales are written), in
+// camera order.  Per unit: the camera (-1 past the unit total), its slot range,
+// the camera's unit count (the last-arrival count) and first unit (its
+// partials are cpart[27 * (first .. first + count))).
+constexpr int kCuStride = 8;
+enum { CU_CAM = 0, CU_BEG, CU_END, CU_COUNT, CU_FIRST };
 
 // Layout of the sharded exchange buffer (one all-reduce per LM iteration after
 // the Schur pass): the reduced camera system in the Schur tile layout
