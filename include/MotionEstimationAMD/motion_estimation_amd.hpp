@@ -870,11 +870,29 @@ class WindowedStereoVO {
   void setMatchLrMax(double lrMax) {
     check(me_vo_loop_set_match_lr(v_.get(), lrMax), "WindowedStereoVO::setMatchLrMax");
   }
-  // keyframe t (0, 1, 2, ...): host images of the configured size, copied in
+  // Rectification inside the loop (me_hip.h A12d, me_vo_loop_set_rectify): with
+  // the two camera models (R = the R1 / R2 of the stereo calibration) process()
+  // and processDevice() take raw images, each of its model's size, and the loop
+  // warps them into the configured width x height and K first; pixels without
+  // a source get `border`.  Before the first process(); clearRectification()
+  // switches it off again.  A bad model or border, or a later call, throws.
+  void setRectification(const me_camera_model& left, const me_camera_model& right, int border = 0) {
+    check(me_vo_loop_set_rectify(v_.get(), &left, &right, border), "WindowedStereoVO::setRectification");
+    raw_[0] = left.width, raw_[1] = left.height, raw_[2] = right.width, raw_[3] = right.height;
+  }
+  void clearRectification() {
+    check(me_vo_loop_set_rectify(v_.get(), nullptr, nullptr, 0), "WindowedStereoVO::clearRectification");
+    raw_[0] = raw_[1] = raw_[2] = raw_[3] = 0;
+  }
+  // keyframe t (0, 1, 2, ...): host images of the configured size (of the
+  // camera models' sizes after setRectification), copied in
   void process(int t, const amd::ImageView& left, const amd::ImageView& right) {
     if (left.empty() || right.empty() || left.step != left.cols || right.step != right.cols)
       throw std::invalid_argument("WindowedStereoVO::process: dense 8-bit images expected");
-    if (left.rows != height_ || left.cols != width_ || right.rows != height_ || right.cols != width_)
+    if (raw_[0]) {
+      if (left.cols != raw_[0] || left.rows != raw_[1] || right.cols != raw_[2] || right.rows != raw_[3])
+        throw std::invalid_argument("WindowedStereoVO::process: raw images of the camera models' sizes expected");
+    } else if (left.rows != height_ || left.cols != width_ || right.rows != height_ || right.cols != width_)
       throw std::invalid_argument("WindowedStereoVO::process: images of the configured width x height expected");
     check(me_vo_loop_process(v_.get(), t, left.data, right.data, ME_HOST), "WindowedStereoVO::process");
   }
@@ -933,6 +951,7 @@ class WindowedStereoVO {
   amd::Context& ba_;
   amd::Context& front_;
   int width_, height_;
+  int raw_[4] = {0, 0, 0, 0};  // left / right raw width, height when the loop rectifies (0: it does not)
   bool masked_ = false;
   std::unique_ptr<me_vo_loop, Del> v_;
 };

@@ -95,7 +95,7 @@ int me_host_free(me_ctx* ctx, void* hptr);
    stream, so time only the families a measurement needs. */
 enum { ME_KT_MI = 0, ME_KT_SCALE_RES = 1, ME_KT_SCALE_NEQ = 2, ME_KT_BA_LINEARIZE = 3, ME_KT_BA_POINTS = 4,
        ME_KT_BA_SCHUR = 5, ME_KT_BA_SOLVE = 6, ME_KT_BA_STEP = 7, ME_KT_KLT = 8, ME_KT_PYR = 9, ME_KT_NMS = 10,
-       ME_KT_CORNERS = 11, ME_KT_COUNT = 16, ME_KT_ALL = 0xffff };
+       ME_KT_CORNERS = 11, ME_KT_RECTIFY = 12, ME_KT_COUNT = 16, ME_KT_ALL = 0xffff };
 int me_timing_enable(me_ctx* ctx, int family_mask);
 int me_timing_read(me_ctx* ctx, int kernel, long* launches, double* total_ms);
 int me_timing_reset(me_ctx* ctx);
@@ -473,6 +473,20 @@ const char* me_vo_loop_last_error(const me_vo_loop* v);
    after the first me_vo_loop_process: ME_ERR_STATE.  (A setter, not a
    me_vo_loop_config field: the struct and the ABI version stay as they are.) */
 int me_vo_loop_set_match_lr(me_vo_loop* v, double lr_max);
+/* Rectification inside the loop (A12d): with two camera models the loop builds
+   their maps once on the front context -- the rectified model is the loop's
+   own width, height and K (fx = K[0], fy = K[4], cx = K[2], cy = K[5]) -- and
+   me_vo_loop_process takes raw images from then on: left is
+   left->width x left->height, right is right->width x right->height (stride =
+   width each; the two sizes may differ).  Both are remapped (me_remap_q5,
+   `border` outside) into loop-owned device buffers on the front-end stream
+   ahead of the KLT, and every later stage reads the rectified pair; the
+   lifetime rule of caller images is unchanged.  Two NULL models switch it off
+   (the default); one NULL model, a bad model or border: ME_ERR_INVALID; after
+   the first me_vo_loop_process: ME_ERR_STATE. */
+struct me_camera_model; /* defined in section A12d below */
+int me_vo_loop_set_rectify(me_vo_loop* v, const struct me_camera_model* left, const struct me_camera_model* right,
+                           int border);
 /* Keyframe t (t = 0, 1, 2, ... in order): left / right 8-bit images of
    width x height (stride = width).  mem = ME_DEVICE: device memory on the
    ctx device, read during this call and the next one (keep it alive until
@@ -660,6 +674,85 @@ int me_vo_new_corners(me_ctx* ctx, const uint8_t* img, int width, int height, in
                       const uint8_t* status, const uint8_t* ok, int n, float margin, int nx, int ny, double cw,
                       double ch, int n_feats, int d_min, const me_corner_params* p, float* out_uv, int32_t* out_lo,
                       int32_t* out_count);
+
+/* ---- A12d: stereo rectification (build-defined; no reference) ------------
+ * The reference assumes undistorted, row-aligned images of one size and one K
+ * and leaves rectification to the caller.  Two primitives: me_rectify_map
+ * builds a fixed-point map from a camera model, me_remap_q5 warps an 8-bit
+ * image through any such map.  The numpy restatement is
+ * uasl_motion_estimation_amd/rectify.py (rectify_map_ref, remap_ref), the
+ * checker; both results are bit-exact.
+ *
+ * me_camera_model: the raw image size, fx fy cx cy, dist = {k1, k2, p1, p2, k3}
+ * (Brown-Conrady) and R (row-major), the rotation from raw-camera to
+ * rectified-camera coordinates (the R1 / R2 of a stereo calibration), used as
+ * given and not re-orthonormalised.  me_rectified_model: the rectified size
+ * and fx fy cx cy, shared by both cameras (the VO loop's K, width, height).
+ *
+ * Map: int32 map[height][width][2], the source coordinates in 1/32 pixel (Q5)
+ * of the rectified pixel at integer (u, v).  FP64, every operation rounded
+ * once, evaluated in the order written, never contracted; divisions are
+ * correctly rounded:
+ *   x  = (u - cx_r) / fx_r            y = (v - cy_r) / fy_r
+ *   X  = (R[0]*x + R[3]*y) + R[6]     Y = (R[1]*x + R[4]*y) + R[7]
+ *   W  = (R[2]*x + R[5]*y) + R[8]                               (R transposed)
+ *   a  = X / W                        b = Y / W
+ *   a2 = a*a    b2 = b*b    r2 = a2 + b2    tab = 2.0*(a*b)
+ *   rad = 1.0 + r2*(k1 + r2*(k2 + r2*k3))
+ *   xd = (a*rad + p1*tab) + p2*(r2 + 2.0*a2)
+ *   yd = (b*rad + p1*(r2 + 2.0*b2)) + p2*tab
+ *   us = fx*xd + cx                   vs = fy*yd + cy
+ * The entry is the sentinel {INT32_MIN, INT32_MIN} ("no source") unless W > 0,
+ * fabs(us) < 2^24 and fabs(vs) < 2^24 (all three false for NaN); otherwise
+ * {(int32)rint(us*32.0), (int32)rint(vs*32.0)}, rint to nearest-even.
+ *
+ * Remap of an 8-bit source (src_w, src_h, src_stride) through a Q5 map of
+ * dst_w x dst_h: for the entry {iu, iv}, sx = iu >> 5 (arithmetic shift:
+ * floor), fxq = iu & 31, sy and fyq likewise; taps (sx, sy), (sx+1, sy),
+ * (sx, sy+1), (sx+1, sy+1); a tap outside [0, src_w) x [0, src_h) has the
+ * value `border` (0..255), each tap judged on its own;
+ *   dst = (p00*(32-fxq)*(32-fyq) + p10*fxq*(32-fyq) + p01*(32-fxq)*fyq
+ *          + p11*fxq*fyq + 512) >> 10.
+ * A sentinel entry gives `border` (all four of its taps lie outside any
+ * image).  Exact integer arithmetic: nothing depends on scheduling.  Bytes of
+ * a row past its width (stride padding) are never read as pixels nor written.
+ *
+ * Arguments: non-finite model parameters, fx or fy <= 0, a size below 1,
+ * border outside 0..255 and a stride below its width are ME_ERR_INVALID with
+ * a message that names the argument; 1 x 1 images are legal on both sides;
+ * width * height < 2^31 on every side.  ME_HOST: every pointer is host memory
+ * and the call is synchronous; ME_DEVICE: every pointer is device memory (the
+ * map 8-byte aligned) and the call is asynchronous on the ctx stream.  Both
+ * are timed in the ME_KT_RECTIFY family. */
+typedef struct me_camera_model {
+  int width, height;          /* raw image */
+  double fx, fy, cx, cy;
+  double dist[5];             /* k1, k2, p1, p2, k3 */
+  double R[9];                /* raw camera -> rectified camera, row-major */
+} me_camera_model;
+typedef struct {
+  int width, height;
+  double fx, fy, cx, cy;
+} me_rectified_model;
+int me_rectify_map(me_ctx* ctx, me_mem mem, const me_camera_model* cam, const me_rectified_model* rect,
+                   int32_t* map /* rect->height * rect->width * 2 */);
+/* me_remap_q5 works on tiles of *tw x *th destination pixels (row-major tile
+   order, ceil(dst_w / tw) tiles per row), one workgroup each.  A tile takes
+   one of two paths, chosen from the map's content alone: the bounding box of
+   the taps of its entries that touch the image (taps clamped to [-1, src_w] x
+   [-1, src_h]; x0 .. x1, y0 .. y1) is staged in LDS as
+   rows = y1 - y0 + 1 rows of words = (x1 >> 2) - (x0 >> 2) + 1 aligned groups
+   of four pixels with a row stride of (words + 1) | 1 words -- path 0 -- iff
+   rows * ((words + 1) | 1) <= *stage_words (arithmetic shifts); otherwise
+   every pixel of the tile reads its taps from global memory -- path 1.  A
+   tile none of whose entries touches the image is path 0.  stage_words may be
+   NULL. */
+int me_remap_tile_dims(int* tw, int* th, int* stage_words);
+/* tile_path (may be NULL): one byte per tile, the path it took (0 staged,
+   1 global).  The output does not depend on the path. */
+int me_remap_q5(me_ctx* ctx, me_mem mem, const uint8_t* src, int src_w, int src_h, int src_stride,
+                const int32_t* map, int dst_w, int dst_h, int border, uint8_t* dst, int dst_stride,
+                uint8_t* tile_path);
 
 /* ---- A11: non-maximum suppression ------------------------------------
  * Replaces std::vector<pt2D> me::nonMaxSupScanline3x3(const cv::Mat& input,

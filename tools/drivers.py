@@ -22,6 +22,10 @@ loads another build of libme_hip.so (tools/build_variant.sh).
                          me_mi_epipolar_match_lr beside me_mi_epipolar_match on a config-3 stereo pair (2000
                          tracked-form and 250 new-form features), alternating in one process, and the config-3
                          native loop with match_lr_max 0 / 1, alternating
+  rectify [--reps --check --loop N]
+                         me_rectify_map and me_remap_q5 (1280x720, 3840x2160) through a realistic camera's map,
+                         beside the library's streaming copy of the same bytes, and the config-3 native loop
+                         with the rectifier off / on (padded frames cropped back), alternating
 """
 import argparse
 import ctypes
@@ -724,6 +728,154 @@ def cmd_match_lr(a):
     print(json.dumps(out))
 
 
+def _realistic_camera(w, h):
+    """A plausible raw camera for a w x h rectified image: k1 -0.3, k2 0.1, small tangential terms,
+    rotations of a degree or two about every axis, slightly different focal lengths and centre."""
+    import math
+
+    from uasl_motion_estimation_amd.rectify import CameraModel, RectifiedModel
+
+    def rot(axis, deg):
+        c, s = math.cos(math.radians(deg)), math.sin(math.radians(deg))
+        i, j = [(1, 2), (2, 0), (0, 1)][axis]
+        R = np.eye(3)
+        R[i, i], R[i, j], R[j, i], R[j, j] = c, -s, s, c
+        return R
+
+    rect = RectifiedModel(w, h, 0.9 * w, 0.9 * w, w / 2.0, h / 2.0)
+    R = rot(0, 1.0) @ rot(1, -1.5) @ rot(2, 0.7)
+    cam = CameraModel(w, h, 0.92 * w, 0.91 * w, w / 2.0 + 3.5, h / 2.0 - 2.25, (-0.3, 0.1, 5e-4, -3e-4, 0.0),
+                      tuple(R.ravel()))
+    return cam, rect
+
+
+def cmd_rectify(a):
+    """The rectifier (csrc/rectify.hip): me_rectify_map once and me_remap_q5
+    --reps times per size (1280x720, 3840x2160) through the map of a realistic
+    camera, HIP-event times of the ME_KT_RECTIFY family; the share of tiles on
+    each path; the rate in algorithmic bytes (8 map + 1 source + 1 destination
+    per pixel) beside me_hbm_copy_gbs moving the same number of bytes.  With
+    --check both results are compared with the numpy restatement at full size.
+    Then the config-3 native loop over --loop corridor keyframes, rectifier off
+    (plain frames) and on (the frames padded by (8, 5) and the camera that
+    crops them back: the same pixels reach the loop), alternating, two timed
+    runs each.  With --lib a -DME_REMAP_NO_STAGE build times the global path
+    alone on the same maps."""
+    ctx = _setup(a.lib)
+    from uasl_motion_estimation_amd import pipeline as PL, rectify as RC, synthetic as S
+
+    V = ctypes.c_void_p
+    out = {"lib": a.lib or "in-tree", "reps": a.reps}
+    ok = True
+    for (W, H) in ((1280, 720), (3840, 2160)):
+        cam, rect = _realistic_camera(W, H)
+        npx = W * H
+        src = np.random.default_rng(5).integers(0, 256, (H, W), dtype=np.uint8)
+        tx, ty = RC.tile_grid(W, H)
+        d_src, d_map, d_dst, d_tp = ctx.malloc(npx), ctx.malloc(8 * npx), ctx.malloc(npx), ctx.malloc(tx * ty)
+        ctx.h2d(d_src, src)
+        cc, rc = cam.to_c(), rect.to_c()
+
+        def build_map():
+            ctx.check(ctx.lib.me_rectify_map(ctx.h, 1, ctypes.byref(cc), ctypes.byref(rc), V(d_map)), "me_rectify_map")
+
+        def warp(tp):
+            ctx.check(ctx.lib.me_remap_q5(ctx.h, 1, V(d_src), W, H, W, V(d_map), W, H, 0, V(d_dst), W,
+                                          V(d_tp) if tp else None), "me_remap_q5")
+
+        build_map()
+        warp(True)
+        ctx.synchronize()
+        ctx.timing(True, ["RECTIFY"])
+        ctx.timing_reset()
+        for _ in range(5):
+            build_map()
+        ctx.synchronize()
+        n_map, ms_map = ctx.timing_read("RECTIFY")
+        for _ in range(20):
+            warp(False)
+        ctx.synchronize()
+        ctx.timing_reset()
+        for _ in range(a.reps):
+            warp(False)
+        ctx.synchronize()
+        n, ms = ctx.timing_read("RECTIFY")
+        ctx.timing(False)
+        gbs = ctypes.c_double()
+        ctx.check(ctx.lib.me_hbm_copy_gbs(ctx.h, 5 * npx, 50, ctypes.byref(gbs)), "me_hbm_copy_gbs")
+        tp = np.zeros(tx * ty, np.uint8)
+        ctx.d2h(tp, d_tp)
+        us = 1e3 * ms / n
+        rate = 10.0 * npx / (us * 1e-6) / 1e9
+        r = {"size": f"{W}x{H}", "rectify_map_us": round(1e3 * ms_map / n_map, 2), "remap_us": round(us, 2),
+             "launches": n, "tiles": int(tp.size), "tiles_global_path": int(tp.sum()),
+             "algorithmic_bytes_per_pixel": 10, "remap_algorithmic_gbs": round(rate, 1),
+             "copy_same_bytes_gbs": round(gbs.value, 1), "fraction_of_copy": round(rate / gbs.value, 3)}
+        if a.check:
+            m = np.zeros((H, W, 2), np.int32)
+            got = np.zeros((H, W), np.uint8)
+            ctx.d2h(m, d_map)
+            ctx.d2h(got, d_dst)
+            mref = RC.rectify_map_ref(cam, rect)
+            r["map_bit_exact"] = bool(np.array_equal(m, mref))
+            r["remap_bit_exact"] = bool(np.array_equal(got, RC.remap_ref(src, mref, 0)))
+            ok = ok and r["map_bit_exact"] and r["remap_bit_exact"]
+        for p in (d_src, d_map, d_dst, d_tp):
+            ctx.free(p)
+        out[r["size"]] = r
+        print(json.dumps(r), flush=True)
+    if not ok:
+        sys.exit(1)
+    if a.loop > 0:
+        import torch
+
+        c, NK = 3, a.loop
+        arc = S.trajectory_arc(max(NK, 2))
+        truth = [np.concatenate([t, S.R_to_aa_robust(Rm)]) for (Rm, t) in arc]
+        K = S.intrinsics(1280, 720)
+        px, py = 8, 5
+        rect = RC.RectifiedModel.from_K(1280, 720, K)
+        cam = RC.CameraModel(1280 + 2 * px, 720 + 2 * py, rect.fx, rect.fy, rect.cx + px, rect.cy + py)
+        rig = RC.StereoRectifier(cam, cam, rect, border=0)
+        frames, padded = [], []
+        for c0 in range(0, NK, 50):
+            _, fr = S.corridor_frames_torch(S.SEED0 + c, 1280, 720, c0, min(50, NK - c0))
+            for (Lk, Rk, _, _) in fr:
+                frames.append((Lk.contiguous(), Rk.contiguous()))
+                padded.append(tuple(torch.nn.functional.pad(im, (px, px, py, py), value=77).contiguous()
+                                    for im in (Lk, Rk)))
+            torch.cuda.synchronize()
+            print(f"rendered {len(frames)} keyframes", flush=True)
+        runs, poses = [], {}
+        for rep in range(-1, 2):  # (-1: a short untimed run, the first loop of a process pays the allocations)
+            for on in (False, True):
+                cfg = PL.PipelineConfig.from_config(c, rectify=rig if on else None)
+                vo = PL.NativeStereoVO(cfg, ctx, K, truth[0], truth[1] - truth[0], log_events=False, overlap=True)
+                seq = padded if on else frames
+                t0 = time.perf_counter()
+                for t in range(NK if rep >= 0 else min(NK, 30)):
+                    vo.process(t, *seq[t])
+                vo.finish()
+                dt = time.perf_counter() - t0
+                if rep < 0:
+                    vo.close()
+                    continue
+                st = vo._stats()
+                res = vo.results
+                poses[on] = np.stack([q.pose for q in res])
+                vo.close()
+                names = ["klt_match", "first_match", "scale_submit", "window_submit", "ba_result", "scale_result"]
+                r = {"rectify": on, "repeat": rep, "keyframes": NK, "keyframes_per_s": round(NK / dt, 2),
+                     "tracked_mean": round(float(np.mean([q.n_tracked for q in res[2:]])), 1),
+                     "host_s": round(st[0], 4), "blocked_s": round(st[1], 4),
+                     "wait_ms_per_keyframe": {k: round(1e3 * st[3 + i] / NK, 4) for i, k in enumerate(names)}}
+                runs.append(r)
+                print(json.dumps(r), flush=True)
+        out["loop_config3"] = runs
+        out["loop_poses_bit_equal"] = bool(np.array_equal(poses[False].view(np.uint64), poses[True].view(np.uint64)))
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--lib", default=os.environ.get("ME_LIB"))
@@ -766,6 +918,10 @@ def main():
     p.add_argument("--loop", type=int, default=200, help="keyframes of the config-3 native loop per run (0: skip)")
     p.add_argument("--plain-only", dest="plain_only", action="store_true",
                    help="me_mi_epipolar_match alone (works on a build without the check: A/B of two trees)")
+    p = sub.add_parser("rectify")
+    p.add_argument("--reps", type=int, default=200)
+    p.add_argument("--check", type=int, default=1)
+    p.add_argument("--loop", type=int, default=200, help="keyframes of the config-3 native loop per run (0: skip)")
     a = ap.parse_args()
     globals()["cmd_" + a.cmd](a)
 

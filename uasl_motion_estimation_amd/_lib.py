@@ -37,7 +37,7 @@ ERRORS = {
 
 # kernel timing families (me_hip.h ME_KT_*)
 KT = dict(MI=0, SCALE_RES=1, SCALE_NEQ=2, BA_LINEARIZE=3, BA_POINTS=4, BA_SCHUR=5, BA_SOLVE=6, BA_STEP=7,
-          KLT=8, PYR=9, NMS=10, CORNERS=11)
+          KLT=8, PYR=9, NMS=10, CORNERS=11, RECTIFY=12)
 
 
 class MEError(RuntimeError):
@@ -151,6 +151,18 @@ class CornerParamsC(ctypes.Structure):
     _fields_ = [("win", c_int), ("min_eig", c_double)]
 
 
+class CameraModelC(ctypes.Structure):
+    """me_camera_model (include/me_hip.h)."""
+    _fields_ = [("width", c_int), ("height", c_int), ("fx", c_double), ("fy", c_double), ("cx", c_double),
+                ("cy", c_double), ("dist", c_double * 5), ("R", c_double * 9)]
+
+
+class RectifiedModelC(ctypes.Structure):
+    """me_rectified_model (include/me_hip.h)."""
+    _fields_ = [("width", c_int), ("height", c_int), ("fx", c_double), ("fy", c_double), ("cx", c_double),
+                ("cy", c_double)]
+
+
 ALLREDUCE_FN = ctypes.CFUNCTYPE(c_int, POINTER(c_double), c_int, c_void_p)
 
 # every symbol include/me_hip.h declares (checked by tests/test_abi.py)
@@ -169,6 +181,7 @@ EXPORTS = [
     "me_comm_allreduce", "me_comm_calibrate", "me_comm_exchange_us", "me_ba_shard_worthwhile_comm", "me_ba_solve_comm", "me_ba_shard_worthwhile", "me_ba_shard_exchange_us",
     "me_klt_default_params", "me_klt_track", "me_klt_track_fb",
     "me_corner_default_params", "me_corner_response", "me_vo_new_corners",
+    "me_rectify_map", "me_remap_tile_dims", "me_remap_q5", "me_vo_loop_set_rectify",
     "me_nms_scanline3x3",
     "me_vo_default_params", "me_vo_srand", "me_vo_rand", "me_vo_process",
     "me_mono_default_params", "me_mono_vo_process",
@@ -323,6 +336,11 @@ def load_library(path: str | None = None):
         "me_vo_new_corners": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                       c_float, c_int, c_int, c_double, c_double, c_int, c_int, P(CornerParamsC),
                                       c_void_p, c_void_p, c_void_p]),
+        "me_rectify_map": (c_int, [c_void_p, c_int, P(CameraModelC), P(RectifiedModelC), c_void_p]),
+        "me_remap_tile_dims": (c_int, [P(c_int), P(c_int), P(c_int)]),
+        "me_remap_q5": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int,
+                                c_void_p, c_int, c_void_p]),
+        "me_vo_loop_set_rectify": (c_int, [c_void_p, P(CameraModelC), P(CameraModelC), c_int]),
         "me_nms_scanline3x3": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
                                        P(c_int)]),
         "me_vo_default_params": (None, [P(VOParamsC)]),

@@ -231,6 +231,15 @@ struct me_vo_loop {
   };
   std::map<int, Imgs> imgs;
   Buf img_slot[3];
+  // ---- rectification (me_vo_loop_set_rectify): the two maps, the raw sizes, one upload buffer for host
+  // images and three rectified pairs (a keyframe's pair is read during its call and the next one, by the
+  // scale LM of the call after as well: the rule of img_slot)
+  bool rectify = false;
+  int rect_border = 0;
+  int raw_w[2] = {0, 0}, raw_h[2] = {0, 0};
+  void* rect_map[2] = {nullptr, nullptr};
+  void* rect_raw = nullptr;
+  void* rect_slot[3] = {nullptr, nullptr, nullptr};
   bool has_prev = false;
   int prev_t = -1;
   // ---- lagged state
@@ -431,6 +440,7 @@ struct me_vo_loop {
       if (w) me_free(ctx, w);
     for (auto& b : img_slot)
       if (b.p) me_free(tctx, b.p);
+    rectify_off();
     for (auto& kv : dev) me_free(tctx, kv.second.p);
     for (auto& kv : pin) me_host_free(tctx, kv.second.p);
     dev.clear();
@@ -487,8 +497,65 @@ struct me_vo_loop {
     }
   }
 
+  void rectify_off() {
+    for (auto& p : rect_map) {
+      if (p) me_free(tctx, p);
+      p = nullptr;
+    }
+    for (auto& p : rect_slot) {
+      if (p) me_free(tctx, p);
+      p = nullptr;
+    }
+    if (rect_raw) me_free(tctx, rect_raw);
+    rect_raw = nullptr;
+    rectify = false;
+  }
+  // The maps of the two cameras, built once on the front context; the rectified model is the loop's own
+  int rectify_on(const me_camera_model* left, const me_camera_model* right, int border) {
+    rectify_off();
+    const me_rectified_model rm{cfg.width, cfg.height, cfg.K[0], cfg.K[4], cfg.K[2], cfg.K[5]};
+    const me_camera_model* cam[2] = {left, right};
+    const size_t npx = (size_t)cfg.width * cfg.height;
+    for (int k = 0; k < 2; ++k) {
+      VL_TRY(me_malloc(tctx, &rect_map[k], 8 * npx), "malloc");
+      VL_TRY(me_rectify_map(tctx, ME_DEVICE, cam[k], &rm, (int32_t*)rect_map[k]), "me_vo_loop_set_rectify");
+      raw_w[k] = cam[k]->width;
+      raw_h[k] = cam[k]->height;
+    }
+    for (auto& p : rect_slot) VL_TRY(me_malloc(tctx, &p, 2 * npx), "malloc");
+    VL_TRY(me_malloc(tctx, &rect_raw, (size_t)raw_w[0] * raw_h[0] + (size_t)raw_w[1] * raw_h[1]), "malloc");
+    VL_TRY(me_synchronize(tctx), "me_vo_loop_set_rectify");
+    rect_border = border;
+    rectify = true;
+    return ME_OK;
+  }
+  // Raw pair -> rectified pair of keyframe t, two remaps queued on the front-end stream ahead of the KLT
+  int frame_images_rectified(int t, const uint8_t* L, const uint8_t* R, me_mem mem) {
+    const size_t nl = (size_t)raw_w[0] * raw_h[0], nr = (size_t)raw_w[1] * raw_h[1];
+    if (mem != ME_DEVICE) {
+      VL_TRY(me_memcpy_async(tctx, rect_raw, L, nl), "image upload");
+      VL_TRY(me_memcpy_async(tctx, (uint8_t*)rect_raw + nl, R, nr), "image upload");
+      L = (const uint8_t*)rect_raw;
+      R = L + nl;
+    }
+    const size_t npx = (size_t)cfg.width * cfg.height;
+    uint8_t* o = (uint8_t*)rect_slot[t % 3];
+    VL_TRY(me_remap_q5(tctx, ME_DEVICE, L, raw_w[0], raw_h[0], raw_w[0], (const int32_t*)rect_map[0], cfg.width,
+                       cfg.height, rect_border, o, cfg.width, nullptr),
+           "me_remap_q5");
+    VL_TRY(me_remap_q5(tctx, ME_DEVICE, R, raw_w[1], raw_h[1], raw_w[1], (const int32_t*)rect_map[1], cfg.width,
+                       cfg.height, rect_border, o + npx, cfg.width, nullptr),
+           "me_remap_q5");
+    Imgs im;
+    im.L = o;
+    im.R = o + npx;
+    imgs[t] = im;
+    return ME_OK;
+  }
+
   int frame_images(int t, const uint8_t* L, const uint8_t* R, me_mem mem) {
     if (imgs.count(t)) return ME_OK;
+    if (rectify) return frame_images_rectified(t, L, R, mem);
     Imgs im;
     if (mem == ME_DEVICE) {
       im.L = L;
@@ -1349,6 +1416,30 @@ int me_vo_loop_set_match_lr(me_vo_loop* v, double lr_max) {
   }
   v->match_lr = lr_max;
   return ME_OK;
+}
+
+int me_vo_loop_set_rectify(me_vo_loop* v, const me_camera_model* left, const me_camera_model* right, int border) {
+  if (!v) return ME_ERR_INVALID;
+  if ((left == nullptr) != (right == nullptr)) {
+    v->err = "me_vo_loop_set_rectify: left and right are both models or both NULL";
+    return ME_ERR_INVALID;
+  }
+  if (left && (border < 0 || border > 255)) {
+    v->err = "me_vo_loop_set_rectify: border must be in 0..255";
+    return ME_ERR_INVALID;
+  }
+  if (v->has_prev || v->failed) {
+    v->err = "me_vo_loop_set_rectify: rectification is set before the first me_vo_loop_process";
+    return ME_ERR_STATE;
+  }
+  me_range range_("me_vo_loop_set_rectify");
+  if (!left) {
+    v->rectify_off();
+    return ME_OK;
+  }
+  const int rc = v->rectify_on(left, right, border);
+  if (rc != ME_OK) v->rectify_off();
+  return rc;
 }
 
 int me_vo_loop_process(me_vo_loop* v, int t, const uint8_t* left, const uint8_t* right, me_mem mem) {

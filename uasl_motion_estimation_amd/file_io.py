@@ -404,14 +404,22 @@ class StereoImageStream:
     so decoding frame k+1 overlaps the device work of frame k).  Yields
     (nb, stamp, dev_left, dev_right, width, height).  Mirrors ImageReader's
     image mode (file_IO.h:300-340): frames before frame_info.fframe are skipped,
-    every frame_info.skip-th frame is used, and reading stops after lframe (if > 0)."""
+    every frame_info.skip-th frame is used, and reading stops after lframe (if > 0).
 
-    def __init__(self, cfg: Config, ctx, image_file: str | None = None, padding: int = 5):
+    With `rectifier` (a rectify.StereoRectifier) the frames are raw: the two
+    cameras may differ in size, so each has slots of its own model's size, a
+    frame of another size is an error, and the stream yields
+    (nb, stamp, dev_left, dev_right, left_width, left_height, right_width,
+    right_height) -- the raw pointers a rectifying loop takes
+    (PipelineConfig.rectify, me_vo_loop_set_rectify)."""
+
+    def __init__(self, cfg: Config, ctx, image_file: str | None = None, padding: int = 5, rectifier=None):
         import torch
 
         self.cfg = cfg
         self.ctx = ctx
         self.padding = padding
+        self.rectifier = rectifier
         d = cfg.dataset_info.dir
         self.file = ImageFile(image_file or os.path.join(d, cfg.dataset_info.image_filename or "image_data.csv"))
         self._torch = torch
@@ -425,6 +433,15 @@ class StereoImageStream:
             dev = torch.device("cuda", self.ctx.device)
             self._dev = [torch.empty((2,) + tuple(shape), dtype=torch.uint8, device=dev) for _ in range(2)]
             self._host = [torch.empty((2,) + tuple(shape), dtype=torch.uint8).pin_memory() for _ in range(2)]
+
+    def _ensure_raw(self):
+        """Per-camera slots of the rectifier's two raw sizes: _dev[s] / _host[s] = (left, right)."""
+        torch = self._torch
+        if self._dev[0] is None:
+            dev = torch.device("cuda", self.ctx.device)
+            shapes = (self.rectifier.left.shape, self.rectifier.right.shape)
+            self._dev = [tuple(torch.empty(sh, dtype=torch.uint8, device=dev) for sh in shapes) for _ in range(2)]
+            self._host = [tuple(torch.empty(sh, dtype=torch.uint8).pin_memory() for sh in shapes) for _ in range(2)]
 
     def __iter__(self):
         fi = self.cfg.frame_info
@@ -446,6 +463,20 @@ class StereoImageStream:
             if left is None or (stereo and right is None):
                 continue
             right = right if right is not None else left
+            if self.rectifier is not None:
+                self.rectifier.check_raw(left.shape, right.shape, f"StereoImageStream: frame {nb}")
+                self._ensure_raw()
+                s = self._slot
+                self._slot ^= 1
+                stream = self._torch.cuda.ExternalStream(self.ctx.stream_ptr(), device=self.ctx.device)
+                for h, d, im in zip(self._host[s], self._dev[s], (left, right)):
+                    h.numpy()[...] = im
+                    with self._torch.cuda.stream(stream):
+                        d.copy_(h, non_blocking=True)
+                dl, dr = self._dev[s]
+                yield (nb, stamp, dl.data_ptr(), dr.data_ptr(), left.shape[1], left.shape[0], right.shape[1],
+                       right.shape[0])
+                continue
             self._ensure(left.shape)
             s = self._slot
             self._slot ^= 1

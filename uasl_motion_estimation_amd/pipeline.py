@@ -126,8 +126,17 @@ class PipelineConfig:
     corner_min_eig: float = 1e-4
     klt_fb_max: float = 0.0       # > 0: forward-backward check of the tracker, bound in pixels (klt_fb_host); 0: off
     match_lr_max: float = 0.0     # > 0: left-right check of the stereo matches, bound in pixels (match_lr_host); 0: off
+    rectify: "StereoRectifier | None" = None  # rectify.StereoRectifier: process() takes raw images and warps them first
 
     def __post_init__(self):
+        if self.rectify is not None:
+            from .rectify import StereoRectifier
+
+            if not isinstance(self.rectify, StereoRectifier):
+                raise ValueError("rectify must be a rectify.StereoRectifier or None")
+            if self.rectify.out.shape != (self.height, self.width):
+                raise ValueError(f"rectify: the rectified model is {self.rectify.out.width} x {self.rectify.out.height}, "
+                                 f"the loop {self.width} x {self.height}")
         if self.detector not in DETECTORS:
             raise ValueError(f"detector must be one of {DETECTORS}")
         if not self.klt_fb_max >= 0.0:  # (false for NaN)
@@ -139,6 +148,12 @@ class PipelineConfig:
     def from_config(c: int, **kw) -> "PipelineConfig":
         cfg = S.CONFIGS[c]
         return PipelineConfig(cfg["width"], cfg["height"], cfg["n_feats"], cfg["window"], **kw)
+
+
+def check_rectifier_K(cfg: "PipelineConfig", K):
+    """The rectified model of cfg.rectify is the loop's own K."""
+    if cfg.rectify is not None and not cfg.rectify.out.matches_K(K):
+        raise ValueError("rectify: the rectified model's fx, fy, cx, cy are not the loop's K")
 
 
 @dataclass
@@ -353,9 +368,24 @@ class Backend:
     detector = ("grid", 21, 1e-4)  # (detector, corner_win, corner_min_eig) of the loop's configuration
     klt_fb_max = 0.0  # PipelineConfig.klt_fb_max of the loop's configuration (0: no forward-backward check)
     match_lr_max = 0.0  # PipelineConfig.match_lr_max of the loop's configuration (0: no left-right check)
+    rectifier = None  # PipelineConfig.rectify of the loop's configuration (None: the images come rectified)
+    rectifies = False  # True: frame_images takes raw images and warps them itself (on the device)
 
     def frame_images(self, t: int, left: np.ndarray, right: np.ndarray):
         raise NotImplementedError
+
+    def rectified_pair(self, left, right):
+        """The pair frame_images gets: a host backend (rectifies = False)
+        warps raw images here with the numpy restatement
+        (StereoRectifier.apply_ref); without a rectifier, or on a backend that
+        warps on the device, the images pass through."""
+        if self.rectifier is None:
+            return left, right
+        left, right = np.asarray(left), np.asarray(right)
+        self.rectifier.check_raw(left.shape, right.shape, "WindowedStereoVO.process")
+        if self.rectifies:
+            return left, right
+        return self.rectifier.apply_ref(left, right)
 
     def new_features(self, t: int, imgs, uv_good: np.ndarray, grid, d_min: int = 0) -> np.ndarray:
         """New features of keyframe t given the good tracked features
@@ -489,6 +519,7 @@ class GPUBackend(Backend):
         self.shared_ctx = self.tctx is self.ctx
         self.async_enqueue = not self.shared_ctx
         self._imgs = {}
+        self._raw = {}  # t -> the raw pair behind a rectified one (device buffers to free, or the caller's tensors)
         # device-resident BA window: obs (4 doubles) | frame | track ID per
         # observation, frame by frame; [_wstart, _wend) live in store _wcur
         self._wcap = 0
@@ -575,6 +606,23 @@ class GPUBackend(Backend):
             return self._map(ptr + offset, nbytes).view(dtype)
         return base[offset:offset + nbytes].view(dtype)
 
+    rectifies = True  # raw images are warped on the front-end context (me_remap_q5), not on the host
+
+    def _rectified(self, t, d_left, d_right, raw):
+        """Handle of keyframe t's rectified pair: two remaps of the raw device
+        images queued on the front-end stream into buffers of the backend's;
+        `raw` (buffers to free, or the caller's tensors) lives until release(t)."""
+        rect = self.rectifier
+        shape = rect.out.shape
+        n = shape[0] * shape[1]
+        oL, oR = self.tctx.malloc(n), self.tctx.malloc(n)
+        rect.apply_device(self.tctx, d_left, d_right, oL, oR)
+        ph = np.lib.stride_tricks.as_strided(np.zeros(1, np.uint8), shape=shape, strides=(0, 0))  # shape only
+        self._raw[t] = raw
+        h = (oL, oR, shape, ph, ph)
+        self._imgs[t] = h
+        return h
+
     def frame_images(self, t, left, right):
         if t in self._imgs:
             return self._imgs[t]
@@ -584,6 +632,9 @@ class GPUBackend(Backend):
         dL, dR = self.tctx.malloc(L.nbytes), self.tctx.malloc(R.nbytes)
         self.tctx.h2d(dL, L)
         self.tctx.h2d(dR, R)
+        if self.rectifier is not None:
+            self.rectifier.check_raw(L.shape, R.shape, "GPUBackend.frame_images")
+            return self._rectified(t, dL, dR, (dL, dR))
         h = (dL, dR, L.shape, L, R)
         self._imgs[t] = h
         return h
@@ -594,8 +645,11 @@ class GPUBackend(Backend):
         referenced until release(t))."""
         if t in self._imgs:
             return self._imgs[t]
+        if self.rectifier is not None:
+            self.rectifier.check_raw(tuple(left.shape), tuple(right.shape), "GPUBackend.frame_images_device")
+            return self._rectified(t, int(left.data_ptr()), int(right.data_ptr()), (left, right))
         shape = tuple(left.shape)
-        ph = np.lib.stride_tricks.as_strided(np.zeros(1, np.uint8), shape=shape, strides=(0, 0))  # shape only
+        ph =np.lib.stride_tricks.as_strided(np.zeros(1, np.uint8), shape=shape, strides=(0, 0))  # shape only
         h = (int(left.data_ptr()), int(right.data_ptr()), shape, ph, ph, (left, right))
         self._imgs[t] = h
         return h
@@ -605,6 +659,9 @@ class GPUBackend(Backend):
         if h is not None and len(h) == 5:  # (device-resident inputs of frame_images_device are the caller's)
             self.tctx.free(h[0])
             self.tctx.free(h[1])
+        for raw in self._raw.pop(t, ()):  # the raw pair behind a rectified one
+            if isinstance(raw, int):
+                self.tctx.free(raw)
 
     def close(self):
         if self._scale_res is not None:
@@ -626,6 +683,8 @@ class GPUBackend(Backend):
         for t in list(self._imgs):
             self.release(t)
         self.tctx.synchronize()
+        if self.rectifier is not None:
+            self.rectifier.release(self.tctx)  # its maps on this context
         for p, _ in self._dev.values():
             self.tctx.free(p)
         self._hview = {}
@@ -1137,10 +1196,12 @@ class WindowedStereoVO:
         self.be.detector = (cfg.detector, cfg.corner_win, cfg.corner_min_eig)
         self.be.klt_fb_max = float(cfg.klt_fb_max)
         self.be.match_lr_max = float(cfg.match_lr_max)
+        self.be.rectifier = cfg.rectify
         if hasattr(backend, "reserve"):
             backend.reserve(cfg)
         self.K = np.asarray(S.intrinsics(cfg.width, cfg.height) if K is None else K, np.float64)
         self.f, self.cx, self.cy = self.K[0, 0], self.K[0, 2], self.K[1, 2]
+        check_rectifier_K(cfg, self.K)
         # grid of feature cells over the margin-free interior
         aw, ah = cfg.width - 2 * MARGIN, cfg.height - 2 * MARGIN
         self.nx = max(1, int(round(math.sqrt(cfg.n_feats * aw / ah))))
@@ -1303,6 +1364,8 @@ class WindowedStereoVO:
         t_in = time.perf_counter()
         w0 = self.stage_s["wait"]
         cfg = self.cfg
+        if self.be.rectifier is not None and left is not None:  # (None: handed to frame_images_device already)
+            left, right = self.be.rectified_pair(left, right)
         imgs = self.be.frame_images(t, left, right)
         # 1. KLT of the active tracks, queued first (it needs only frame t-1's features)
         kh = None
@@ -1626,6 +1689,7 @@ class NativeStereoVO:
             self._masked = True
         self.lib = self.ctx.lib
         self.K = np.asarray(S.intrinsics(cfg.width, cfg.height) if K is None else K, np.float64)
+        check_rectifier_K(cfg, self.K)
         c = VOLoopConfigC()
         self.lib.me_vo_loop_default_config(ctypes.byref(c))
         c.width, c.height, c.n_feats, c.window = cfg.width, cfg.height, cfg.n_feats, cfg.window
@@ -1649,6 +1713,10 @@ class NativeStereoVO:
         # (a setter, not a configuration field: me_vo_loop_config keeps its layout)
         try:
             self._check(self.lib.me_vo_loop_set_match_lr(self.h, float(cfg.match_lr_max)), "me_vo_loop_set_match_lr")
+            if cfg.rectify is not None:  # the loop builds the two maps itself, on its front context
+                cl, cr = cfg.rectify.left.to_c(), cfg.rectify.right.to_c()
+                self._check(self.lib.me_vo_loop_set_rectify(self.h, ctypes.byref(cl), ctypes.byref(cr),
+                                                            int(cfg.rectify.border)), "me_vo_loop_set_rectify")
         except Exception:
             self.close()  # (the loop exists: destroy it, give the contexts their CUs back)
             raise
@@ -1697,10 +1765,14 @@ class NativeStereoVO:
         from ._lib import ME_DEVICE, ME_HOST
 
         shape = (self.cfg.height, self.cfg.width)
+        shapes = {"left": shape, "right": shape}
+        if self.cfg.rectify is not None:  # raw images: each camera model's own size
+            shapes = {"left": self.cfg.rectify.left.shape, "right": self.cfg.rectify.right.shape}
         if hasattr(left, "data_ptr"):
             import torch
 
             for name, im in (("left", left), ("right", right)):
+                shape = shapes[name]
                 if not (isinstance(im, torch.Tensor) and im.dtype == torch.uint8 and tuple(im.shape) == shape
                         and im.is_contiguous() and im.is_cuda and im.device.index == self.ctx.device):
                     raise ValueError(f"NativeStereoVO.process: {name} must be a contiguous uint8 tensor of shape "
@@ -1715,6 +1787,7 @@ class NativeStereoVO:
         else:
             L, R = np.asarray(left), np.asarray(right)
             for name, im in (("left", L), ("right", R)):
+                shape = shapes[name]
                 if im.dtype != np.uint8 or im.shape != shape:
                     raise ValueError(f"NativeStereoVO.process: {name} must be a uint8 array of shape {shape}, "
                                      f"got {im.dtype} {im.shape}")
