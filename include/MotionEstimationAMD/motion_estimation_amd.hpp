@@ -818,6 +818,25 @@ inline std::vector<double> cornerResponse(const amd::ImageView& img, int win = 2
   return out;
 }
 
+namespace amd {
+// Local contrast equalisation of an 8-bit image (A12e, no reference
+// counterpart; build-defined and integer-only, OpenCV parity unpinned):
+// me_clahe on host memory.  Returns the equalised image, rows x cols bytes,
+// dense; `lut` (optional) receives the tiles_y * tiles_x tables of 256 bytes.
+inline std::vector<uint8_t> clahe(const ImageView& img, int tilesX = 8, int tilesY = 8, double clipLimit = 3.0,
+                                  std::vector<uint8_t>* lut = nullptr, Context& ctx = Context::thread_default()) {
+  if (img.empty()) throw std::invalid_argument("clahe: empty image");
+  const me_clahe_params p{tilesX, tilesY, clipLimit};
+  std::vector<uint8_t> out((size_t)img.rows * img.cols);
+  // (sized for any tile counts: bad ones are me_clahe's to refuse)
+  if (lut) lut->assign((size_t)(tilesX > 0 ? tilesX : 0) * (size_t)(tilesY > 0 ? tilesY : 0) * 256, 0);
+  ctx.check(me_clahe(ctx.get(), ME_HOST, img.data, img.cols, img.rows, img.step, &p, out.data(), img.cols,
+                     lut && !lut->empty() ? lut->data() : nullptr),
+            "clahe");
+  return out;
+}
+}  // namespace amd
+
 // The windowed stereo VO loop (me_vo_loop_*, csrc/vo_loop.hip): the
 // application loop the reference leaves to its caller -- per keyframe KLT,
 // epipolar MI matching, WBA_Point bookkeeping (feature_types.h:121-197),
@@ -884,6 +903,17 @@ class WindowedStereoVO {
     check(me_vo_loop_set_rectify(v_.get(), nullptr, nullptr, 0), "WindowedStereoVO::clearRectification");
     raw_[0] = raw_[1] = raw_[2] = raw_[3] = 0;
   }
+  // Local contrast equalisation inside the loop (me_hip.h A12e,
+  // me_vo_loop_set_equalise): both images of every keyframe are equalised on
+  // the front-end stream ahead of the KLT (after the warp when the loop also
+  // rectifies) and every later stage reads the equalised pair; images handed to
+  // processDevice() are not written.  Before the first process();
+  // clearEqualise() switches it off again.  Bad parameters, or a later call, throw.
+  void setEqualise(int tilesX = 8, int tilesY = 8, double clipLimit = 3.0) {
+    const me_clahe_params p{tilesX, tilesY, clipLimit};
+    check(me_vo_loop_set_equalise(v_.get(), &p), "WindowedStereoVO::setEqualise");
+  }
+  void clearEqualise() { check(me_vo_loop_set_equalise(v_.get(), nullptr), "WindowedStereoVO::clearEqualise"); }
   // keyframe t (0, 1, 2, ...): host images of the configured size (of the
   // camera models' sizes after setRectification), copied in
   void process(int t, const amd::ImageView& left, const amd::ImageView& right) {

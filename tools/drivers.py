@@ -26,6 +26,10 @@ loads another build of libme_hip.so (tools/build_variant.sh).
                          me_rectify_map and me_remap_q5 (1280x720, 3840x2160) through a realistic camera's map,
                          beside the library's streaming copy of the same bytes, and the config-3 native loop
                          with the rectifier off / on (padded frames cropped back), alternating
+  clahe [--reps --check --loop N]
+                         me_clahe (1280x720, 3840x2160; noise and a 16-level low-contrast image, 8x8 tiles), the
+                         table kernel and the apply kernel apart, beside the library's streaming copy of the same
+                         bytes, and the config-3 native loop with the equaliser off / on, alternating
 """
 import argparse
 import ctypes
@@ -876,6 +880,132 @@ def cmd_rectify(a):
     print(json.dumps(out))
 
 
+def _low_contrast(w, h, seed=5):
+    """A 16-level image: uniform noise smoothed twice with the 5-point cross average, 100 + v // 16."""
+    a = np.random.default_rng(seed).random((h, w))
+    for _ in range(2):
+        a = (a + np.roll(a, 1, 0) + np.roll(a, -1, 0) + np.roll(a, 1, 1) + np.roll(a, -1, 1)) / 5.0
+    v = np.rint(255.0 * (a - a.min()) / (a.max() - a.min())).astype(np.int64)
+    return (100 + v // 16).astype(np.uint8)
+
+
+def cmd_clahe(a):
+    """The equaliser (csrc/clahe.hip): me_clahe --reps times after 20 warm-up
+    calls per size (1280x720, 3840x2160) and image (noise; the 16-level
+    low-contrast image, on which the lanes of a wave meet on a few histogram
+    words), 8 x 8 tiles, clip 3.0, HIP-event times of the ME_KT_CLAHE family.
+    A call launches the table kernel, then the apply kernel: one timed run
+    takes every launch (table + apply), a second one every other launch
+    (me_timing_sample(2): the table kernels), the apply kernel is the
+    difference.  The yardstick is me_hbm_copy_gbs moving the same algorithmic
+    bytes: one read pass for the table, one read and one write per pixel for
+    the apply.  With --check image and tables are compared with the numpy
+    restatement at full size.  Then the config-3 native loop over --loop
+    corridor keyframes, equaliser off and on, alternating, two timed runs each."""
+    ctx = _setup(a.lib)
+    from uasl_motion_estimation_amd import equalise as EQ, pipeline as PL, synthetic as S
+
+    V = ctypes.c_void_p
+    out = {"lib": a.lib or "in-tree", "reps": a.reps}
+    ok = True
+    params = EQ.Clahe()
+    pc = params.to_c()
+    for (W, H) in ((1280, 720), (3840, 2160)):
+        npx = W * H
+        nlut = params.tiles_x * params.tiles_y * 256
+        gb_t, gb_a = ctypes.c_double(), ctypes.c_double()
+        # (the copy reads and writes its buffer once: npx / 2 bytes move npx, npx bytes move 2 npx)
+        ctx.check(ctx.lib.me_hbm_copy_gbs(ctx.h, npx // 2, 50, ctypes.byref(gb_t)), "me_hbm_copy_gbs")
+        ctx.check(ctx.lib.me_hbm_copy_gbs(ctx.h, npx, 50, ctypes.byref(gb_a)), "me_hbm_copy_gbs")
+        for name in ("noise", "low"):
+            src = (np.random.default_rng(5).integers(0, 256, (H, W), dtype=np.uint8) if name == "noise"
+                   else _low_contrast(W, H))
+            d_src, d_dst, d_lut = ctx.malloc(npx), ctx.malloc(npx), ctx.malloc(nlut)
+            ctx.h2d(d_src, src)
+
+            def call():
+                ctx.check(ctx.lib.me_clahe(ctx.h, 1, V(d_src), W, H, W, ctypes.byref(pc), V(d_dst), W, V(d_lut)),
+                          "me_clahe")
+
+            for _ in range(20):
+                call()
+            ctx.synchronize()
+            ctx.timing(True, ["CLAHE"])
+            res = []
+            for every in (1, 2):
+                ctx.timing_sample(every)
+                ctx.timing_reset()
+                for _ in range(a.reps):
+                    call()
+                ctx.synchronize()
+                res.append(ctx.timing_read("CLAHE"))
+            ctx.timing_sample(1)
+            ctx.timing(False)
+            (n_all, ms_all), (n_tab, ms_tab) = res
+            assert n_all == 2 * a.reps and n_tab == a.reps, (n_all, n_tab)
+            both_us, table_us = 1e3 * ms_all / a.reps, 1e3 * ms_tab / n_tab
+            apply_us = both_us - table_us
+            copy_t, copy_a = npx / gb_t.value * 1e-3, 2.0 * npx / gb_a.value * 1e-3  # us
+            r = {"size": f"{W}x{H}", "image": name, "calls": a.reps, "table_us": round(table_us, 2),
+                 "apply_us": round(apply_us, 2), "both_us": round(both_us, 2),
+                 "copy_same_bytes_table_us": round(copy_t, 2), "copy_same_bytes_apply_us": round(copy_a, 2),
+                 "table_fraction_of_copy": round(copy_t / table_us, 3),
+                 "apply_fraction_of_copy": round(copy_a / apply_us, 3)}
+            if a.check:
+                got, lut = np.zeros((H, W), np.uint8), np.zeros((params.tiles_y, params.tiles_x, 256), np.uint8)
+                ctx.d2h(got, d_dst)
+                ctx.d2h(lut, d_lut)
+                want, want_lut = EQ.clahe_ref(src, params)
+                r["lut_bit_exact"] = bool(np.array_equal(lut, want_lut))
+                r["image_bit_exact"] = bool(np.array_equal(got, want))
+                ok = ok and r["lut_bit_exact"] and r["image_bit_exact"]
+            for p in (d_src, d_dst, d_lut):
+                ctx.free(p)
+            out[f"{r['size']}_{name}"] = r
+            print(json.dumps(r), flush=True)
+    if not ok:
+        sys.exit(1)
+    if a.loop > 0:
+        import torch
+
+        c, NK = 3, a.loop
+        arc = S.trajectory_arc(max(NK, 2))
+        truth = [np.concatenate([t, S.R_to_aa_robust(Rm)]) for (Rm, t) in arc]
+        K = S.intrinsics(1280, 720)
+        frames = []
+        for c0 in range(0, NK, 50):
+            _, fr = S.corridor_frames_torch(S.SEED0 + c, 1280, 720, c0, min(50, NK - c0))
+            for (Lk, Rk, _, _) in fr:
+                frames.append((Lk.contiguous(), Rk.contiguous()))
+            torch.cuda.synchronize()
+            print(f"rendered {len(frames)} keyframes", flush=True)
+        runs = []
+        for rep in range(-1, 2):  # (-1: a short untimed run, the first loop of a process pays the allocations)
+            for on in (False, True):
+                cfg = PL.PipelineConfig.from_config(c, equalise=params if on else None)
+                vo = PL.NativeStereoVO(cfg, ctx, K, truth[0], truth[1] - truth[0], log_events=False, overlap=True)
+                t0 = time.perf_counter()
+                for t in range(NK if rep >= 0 else min(NK, 30)):
+                    vo.process(t, *frames[t])
+                vo.finish()
+                dt = time.perf_counter() - t0
+                if rep < 0:
+                    vo.close()
+                    continue
+                st = vo._stats()
+                res = vo.results
+                vo.close()
+                names = ["klt_match", "first_match", "scale_submit", "window_submit", "ba_result", "scale_result"]
+                r = {"equalise": on, "repeat": rep, "keyframes": NK, "keyframes_per_s": round(NK / dt, 2),
+                     "tracked_mean": round(float(np.mean([q.n_tracked for q in res[2:]])), 1),
+                     "host_s": round(st[0], 4), "blocked_s": round(st[1], 4),
+                     "wait_ms_per_keyframe": {k: round(1e3 * st[3 + i] / NK, 4) for i, k in enumerate(names)}}
+                runs.append(r)
+                print(json.dumps(r), flush=True)
+        out["loop_config3"] = runs
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--lib", default=os.environ.get("ME_LIB"))
@@ -919,6 +1049,10 @@ def main():
     p.add_argument("--plain-only", dest="plain_only", action="store_true",
                    help="me_mi_epipolar_match alone (works on a build without the check: A/B of two trees)")
     p = sub.add_parser("rectify")
+    p.add_argument("--reps", type=int, default=200)
+    p.add_argument("--check", type=int, default=1)
+    p.add_argument("--loop", type=int, default=200, help="keyframes of the config-3 native loop per run (0: skip)")
+    p = sub.add_parser("clahe")
     p.add_argument("--reps", type=int, default=200)
     p.add_argument("--check", type=int, default=1)
     p.add_argument("--loop", type=int, default=200, help="keyframes of the config-3 native loop per run (0: skip)")

@@ -10,9 +10,11 @@ kernels + on-device Schur on FP64 MFMA), behind the C ABI of include/me_hip.h
 from ._lib import Context, MEError, default_context, device_count, load_library  # noqa: F401
 from .corners import (corner_params, corner_response, corner_response_ref, new_corners,  # noqa: F401
                       new_corners_ref)
+from .equalise import Clahe, clahe, clahe_ref  # noqa: F401
 from .rectify import (CameraModel, RectifiedModel, StereoRectifier, rectify_map, rectify_map_ref,  # noqa: F401
                       remap, remap_ref)
 
 __all__ = ["Context", "MEError", "default_context", "device_count", "load_library", "corner_params",
-           "corner_response", "corner_response_ref", "new_corners", "new_corners_ref", "CameraModel",
+           "corner_response", "corner_response_ref", "new_corners", "new_corners_ref", "Clahe", "clahe",
+           "clahe_ref", "CameraModel",
            "RectifiedModel", "StereoRectifier", "rectify_map", "rectify_map_ref", "remap", "remap_ref"]

@@ -37,7 +37,7 @@ ERRORS = {
 
 # kernel timing families (me_hip.h ME_KT_*)
 KT = dict(MI=0, SCALE_RES=1, SCALE_NEQ=2, BA_LINEARIZE=3, BA_POINTS=4, BA_SCHUR=5, BA_SOLVE=6, BA_STEP=7,
-          KLT=8, PYR=9, NMS=10, CORNERS=11, RECTIFY=12)
+          KLT=8, PYR=9, NMS=10, CORNERS=11, RECTIFY=12, CLAHE=13)
 
 
 class MEError(RuntimeError):
@@ -163,6 +163,11 @@ class RectifiedModelC(ctypes.Structure):
                 ("cy", c_double)]
 
 
+class ClaheParamsC(ctypes.Structure):
+    """me_clahe_params (include/me_hip.h)."""
+    _fields_ = [("tiles_x", c_int), ("tiles_y", c_int), ("clip_limit", c_double)]
+
+
 ALLREDUCE_FN = ctypes.CFUNCTYPE(c_int, POINTER(c_double), c_int, c_void_p)
 
 # every symbol include/me_hip.h declares (checked by tests/test_abi.py)
@@ -182,6 +187,7 @@ EXPORTS = [
     "me_klt_default_params", "me_klt_track", "me_klt_track_fb",
     "me_corner_default_params", "me_corner_response", "me_vo_new_corners",
     "me_rectify_map", "me_remap_tile_dims", "me_remap_q5", "me_vo_loop_set_rectify",
+    "me_clahe_default_params", "me_clahe", "me_clahe_apply_rows", "me_vo_loop_set_equalise",
     "me_nms_scanline3x3",
     "me_vo_default_params", "me_vo_srand", "me_vo_rand", "me_vo_process",
     "me_mono_default_params", "me_mono_vo_process",
@@ -341,6 +347,11 @@ def load_library(path: str | None = None):
         "me_remap_q5": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int,
                                 c_void_p, c_int, c_void_p]),
         "me_vo_loop_set_rectify": (c_int, [c_void_p, P(CameraModelC), P(CameraModelC), c_int]),
+        "me_clahe_default_params": (None, [P(ClaheParamsC)]),
+        "me_clahe": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, P(ClaheParamsC), c_void_p, c_int,
+                             c_void_p]),
+        "me_clahe_apply_rows": (c_int, [c_void_p, c_int, c_int]),
+        "me_vo_loop_set_equalise": (c_int, [c_void_p, P(ClaheParamsC)]),
         "me_nms_scanline3x3": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
                                        P(c_int)]),
         "me_vo_default_params": (None, [P(VOParamsC)]),

@@ -113,6 +113,9 @@ int me_scratch(me_ctx* ctx, int slot, size_t bytes, void** out);
 int me_pinned(me_ctx* ctx, size_t bytes, void** out);
 int me_check_launch(me_ctx* ctx, const char* what);
 
+// me_clahe's parameter checks against an image size (clahe.hip): NULL, or the message naming the argument.
+const char* me_clahe_check(const me_clahe_params* p, int width, int height);
+
 // roctx range (rocprofv3 --marker-trace) around an entry point's host work.
 struct me_range {
   explicit me_range(const char* name);
@@ -137,6 +140,6 @@ enum {
   SLOT_IMG_L = 0, SLOT_IMG_R, SLOT_XY_L, SLOT_XY_R, SLOT_MI_OUT, SLOT_RED, SLOT_GENERIC,
   SLOT_SC_TRACKS, SLOT_SC_RES, SLOT_SC_RES2, SLOT_SC_NEQ, SLOT_SC_IMGL, SLOT_SC_IMGR,
   SLOT_KLT_PYR, SLOT_KLT_PTS, SLOT_NMS, SLOT_VO, SLOT_EPI, SLOT_MONO, SLOT_CORNERS,
-  SLOT_RECTIFY,
+  SLOT_RECTIFY, SLOT_CLAHE,
   SLOT_COUNT
 };

@@ -240,6 +240,11 @@ struct me_vo_loop {
   void* rect_map[2] = {nullptr, nullptr};
   void* rect_raw = nullptr;
   void* rect_slot[3] = {nullptr, nullptr, nullptr};
+  // ---- equalisation (me_vo_loop_set_equalise): the parameters and, for caller-owned device images only,
+  // three equalised pairs (allocated on first use; the rule of img_slot)
+  bool equalise = false;
+  me_clahe_params eq_params{};
+  void* eq_slot[3] = {nullptr, nullptr, nullptr};
   bool has_prev = false;
   int prev_t = -1;
   // ---- lagged state
@@ -441,6 +446,7 @@ struct me_vo_loop {
     for (auto& b : img_slot)
       if (b.p) me_free(tctx, b.p);
     rectify_off();
+    equalise_off();
     for (auto& kv : dev) me_free(tctx, kv.second.p);
     for (auto& kv : pin) me_host_free(tctx, kv.second.p);
     dev.clear();
@@ -549,7 +555,38 @@ struct me_vo_loop {
     Imgs im;
     im.L = o;
     im.R = o + npx;
+    if (equalise) {
+      const int rc = equalise_pair(t, im, true);
+      if (rc != ME_OK) return rc;
+    }
     imgs[t] = im;
+    return ME_OK;
+  }
+
+  void equalise_off() {
+    for (auto& p : eq_slot) {
+      if (p) me_free(tctx, p);
+      p = nullptr;
+    }
+    equalise = false;
+  }
+  // Keyframe t's pair -> its equalised pair, two me_clahe queued on the front-end stream ahead of the KLT:
+  // in place where the loop owns the images, into eq_slot[t % 3] where they are the caller's
+  int equalise_pair(int t, Imgs& im, bool loop_owned) {
+    const size_t npx = (size_t)cfg.width * cfg.height;
+    uint8_t *oL = const_cast<uint8_t*>(im.L), *oR = const_cast<uint8_t*>(im.R);
+    if (!loop_owned) {
+      void*& p = eq_slot[t % 3];
+      if (p == nullptr) VL_TRY(me_malloc(tctx, &p, 2 * npx), "malloc");
+      oL = (uint8_t*)p;
+      oR = oL + npx;
+    }
+    VL_TRY(me_clahe(tctx, ME_DEVICE, im.L, cfg.width, cfg.height, cfg.width, &eq_params, oL, cfg.width, nullptr),
+           "me_clahe");
+    VL_TRY(me_clahe(tctx, ME_DEVICE, im.R, cfg.width, cfg.height, cfg.width, &eq_params, oR, cfg.width, nullptr),
+           "me_clahe");
+    im.L = oL;
+    im.R = oR;
     return ME_OK;
   }
 
@@ -571,6 +608,10 @@ struct me_vo_loop {
       VL_TRY(me_memcpy_async(tctx, (uint8_t*)b.p + nb, R, nb), "image upload");
       im.L = (const uint8_t*)b.p;
       im.R = (const uint8_t*)b.p + nb;
+    }
+    if (equalise) {
+      const int rc = equalise_pair(t, im, mem != ME_DEVICE);
+      if (rc != ME_OK) return rc;
     }
     imgs[t] = im;
     return ME_OK;
@@ -1440,6 +1481,23 @@ int me_vo_loop_set_rectify(me_vo_loop* v, const me_camera_model* left, const me_
   const int rc = v->rectify_on(left, right, border);
   if (rc != ME_OK) v->rectify_off();
   return rc;
+}
+
+int me_vo_loop_set_equalise(me_vo_loop* v, const me_clahe_params* p) {
+  if (!v) return ME_ERR_INVALID;
+  if (v->has_prev || v->failed) {
+    v->err = "me_vo_loop_set_equalise: equalisation is set before the first me_vo_loop_process";
+    return ME_ERR_STATE;
+  }
+  v->equalise_off();
+  if (!p) return ME_OK;
+  if (const char* why = me_clahe_check(p, v->cfg.width, v->cfg.height)) {
+    v->err = std::string("me_vo_loop_set_equalise: ") + why;
+    return ME_ERR_INVALID;
+  }
+  v->eq_params = *p;
+  v->equalise = true;
+  return ME_OK;
 }
 
 int me_vo_loop_process(me_vo_loop* v, int t, const uint8_t* left, const uint8_t* right, me_mem mem) {

@@ -127,6 +127,7 @@ class PipelineConfig:
     klt_fb_max: float = 0.0       # > 0: forward-backward check of the tracker, bound in pixels (klt_fb_host); 0: off
     match_lr_max: float = 0.0     # > 0: left-right check of the stereo matches, bound in pixels (match_lr_host); 0: off
     rectify: "StereoRectifier | None" = None  # rectify.StereoRectifier: process() takes raw images and warps them first
+    equalise: "Clahe | None" = None  # equalise.Clahe: both images of a keyframe are equalised ahead of the tracker
 
     def __post_init__(self):
         if self.rectify is not None:
@@ -137,6 +138,12 @@ class PipelineConfig:
             if self.rectify.out.shape != (self.height, self.width):
                 raise ValueError(f"rectify: the rectified model is {self.rectify.out.width} x {self.rectify.out.height}, "
                                  f"the loop {self.width} x {self.height}")
+        if self.equalise is not None:
+            from .equalise import Clahe
+
+            if not isinstance(self.equalise, Clahe):
+                raise ValueError("equalise must be an equalise.Clahe or None")
+            self.equalise.check_size(self.width, self.height, "equalise")
         if self.detector not in DETECTORS:
             raise ValueError(f"detector must be one of {DETECTORS}")
         if not self.klt_fb_max >= 0.0:  # (false for NaN)
@@ -370,6 +377,8 @@ class Backend:
     match_lr_max = 0.0  # PipelineConfig.match_lr_max of the loop's configuration (0: no left-right check)
     rectifier = None  # PipelineConfig.rectify of the loop's configuration (None: the images come rectified)
     rectifies = False  # True: frame_images takes raw images and warps them itself (on the device)
+    equaliser = None  # PipelineConfig.equalise of the loop's configuration (None: the images are used as they come)
+    equalises = False  # True: frame_images equalises itself (on the device)
 
     def frame_images(self, t: int, left: np.ndarray, right: np.ndarray):
         raise NotImplementedError
@@ -386,6 +395,17 @@ class Backend:
         if self.rectifies:
             return left, right
         return self.rectifier.apply_ref(left, right)
+
+    def equalised_pair(self, left, right):
+        """The pair frame_images gets, after rectified_pair: a host backend
+        (equalises = False) equalises here with the numpy restatement
+        (equalise.clahe_ref); without the switch, or on a backend that
+        equalises on the device, the images pass through."""
+        if self.equaliser is None or self.equalises:
+            return left, right
+        from .equalise import clahe_ref
+
+        return clahe_ref(left, self.equaliser)[0], clahe_ref(right, self.equaliser)[0]
 
     def new_features(self, t: int, imgs, uv_good: np.ndarray, grid, d_min: int = 0) -> np.ndarray:
         """New features of keyframe t given the good tracked features
@@ -607,6 +627,7 @@ class GPUBackend(Backend):
         return base[offset:offset + nbytes].view(dtype)
 
     rectifies = True  # raw images are warped on the front-end context (me_remap_q5), not on the host
+    equalises = True  # me_clahe on the front-end context, not on the host
 
     def _rectified(self, t, d_left, d_right, raw):
         """Handle of keyframe t's rectified pair: two remaps of the raw device
@@ -617,11 +638,20 @@ class GPUBackend(Backend):
         n = shape[0] * shape[1]
         oL, oR = self.tctx.malloc(n), self.tctx.malloc(n)
         rect.apply_device(self.tctx, d_left, d_right, oL, oR)
+        self._equalise(oL, oR, oL, oR, shape)  # (in place: the rectified buffers are the backend's)
         ph = np.lib.stride_tricks.as_strided(np.zeros(1, np.uint8), shape=shape, strides=(0, 0))  # shape only
         self._raw[t] = raw
         h = (oL, oR, shape, ph, ph)
         self._imgs[t] = h
         return h
+
+    def _equalise(self, d_left, d_right, d_out_left, d_out_right, shape):
+        """With the switch on: two me_clahe queued on the front-end stream, dense device images."""
+        if self.equaliser is not None:
+            from .equalise import clahe_device
+
+            clahe_device(self.tctx, self.equaliser, d_left, shape[1], shape[0], d_out_left)
+            clahe_device(self.tctx, self.equaliser, d_right, shape[1], shape[0], d_out_right)
 
     def frame_images(self, t, left, right):
         if t in self._imgs:
@@ -635,6 +665,7 @@ class GPUBackend(Backend):
         if self.rectifier is not None:
             self.rectifier.check_raw(L.shape, R.shape, "GPUBackend.frame_images")
             return self._rectified(t, dL, dR, (dL, dR))
+        self._equalise(dL, dR, dL, dR, L.shape)  # (in place: the uploaded copies are the backend's)
         h = (dL, dR, L.shape, L, R)
         self._imgs[t] = h
         return h
@@ -650,6 +681,14 @@ class GPUBackend(Backend):
             return self._rectified(t, int(left.data_ptr()), int(right.data_ptr()), (left, right))
         shape = tuple(left.shape)
         ph =np.lib.stride_tricks.as_strided(np.zeros(1, np.uint8), shape=shape, strides=(0, 0))  # shape only
+        if self.equaliser is not None:  # the caller's images are never written: equalised into buffers of the backend's
+            n = shape[0] * shape[1]
+            oL, oR = self.tctx.malloc(n), self.tctx.malloc(n)
+            self._equalise(int(left.data_ptr()), int(right.data_ptr()), oL, oR, shape)
+            self._raw[t] = (left, right)
+            h = (oL, oR, shape, ph, ph)
+            self._imgs[t] = h
+            return h
         h = (int(left.data_ptr()), int(right.data_ptr()), shape, ph, ph, (left, right))
         self._imgs[t] = h
         return h
@@ -1197,6 +1236,7 @@ class WindowedStereoVO:
         self.be.klt_fb_max = float(cfg.klt_fb_max)
         self.be.match_lr_max = float(cfg.match_lr_max)
         self.be.rectifier = cfg.rectify
+        self.be.equaliser = cfg.equalise
         if hasattr(backend, "reserve"):
             backend.reserve(cfg)
         self.K = np.asarray(S.intrinsics(cfg.width, cfg.height) if K is None else K, np.float64)
@@ -1366,6 +1406,8 @@ class WindowedStereoVO:
         cfg = self.cfg
         if self.be.rectifier is not None and left is not None:  # (None: handed to frame_images_device already)
             left, right = self.be.rectified_pair(left, right)
+        if self.be.equaliser is not None and left is not None:
+            left, right = self.be.equalised_pair(left, right)
         imgs = self.be.frame_images(t, left, right)
         # 1. KLT of the active tracks, queued first (it needs only frame t-1's features)
         kh = None
@@ -1717,6 +1759,9 @@ class NativeStereoVO:
                 cl, cr = cfg.rectify.left.to_c(), cfg.rectify.right.to_c()
                 self._check(self.lib.me_vo_loop_set_rectify(self.h, ctypes.byref(cl), ctypes.byref(cr),
                                                             int(cfg.rectify.border)), "me_vo_loop_set_rectify")
+            if cfg.equalise is not None:
+                pc = cfg.equalise.to_c()
+                self._check(self.lib.me_vo_loop_set_equalise(self.h, ctypes.byref(pc)), "me_vo_loop_set_equalise")
         except Exception:
             self.close()  # (the loop exists: destroy it, give the contexts their CUs back)
             raise
