@@ -803,6 +803,54 @@ inline void calcOpticalFlowPyrLK(const amd::ImageView& prev, const amd::ImageVie
             "calcOpticalFlowPyrLK");
 }
 
+// Guided tracking (A12f, me_klt_track_guided; OpenCV's OPTFLOW_USE_INITIAL_FLOW):
+// initial_flow[i] is where feature i's search starts in next (level-0 pixels).
+// An entry that is not finite or lies outside the image is ignored: that
+// feature is tracked from pts_in[i], as by the plain overload.
+inline void calcOpticalFlowPyrLK(const amd::ImageView& prev, const amd::ImageView& next,
+                                 const std::vector<Point2f>& pts_in, const std::vector<Point2f>& initial_flow,
+                                 std::vector<Point2f>& pts_out, std::vector<uint8_t>& status,
+                                 amd::Context& ctx = amd::Context::thread_default()) {
+  if (prev.rows != next.rows || prev.cols != next.cols || prev.step != next.step)
+    throw std::invalid_argument("calcOpticalFlowPyrLK: images differ in shape");
+  if (initial_flow.size() != pts_in.size())
+    throw std::invalid_argument("calcOpticalFlowPyrLK: initial_flow holds one point per feature");
+  pts_out.resize(pts_in.size());
+  status.assign(pts_in.size(), 0);
+  if (pts_in.empty()) return;
+  me_klt_params kp;
+  me_klt_default_params(&kp);
+  ctx.check(me_klt_track_guided(ctx.get(), ME_HOST, prev.data, next.data, prev.cols, prev.rows, prev.step,
+                                &pts_in[0].x, &initial_flow[0].x, &pts_out[0].x, status.data(), (int)pts_in.size(),
+                                &kp),
+            "calcOpticalFlowPyrLK");
+}
+
+// Guided tracking with the forward-backward check (A12f, me_klt_track_guided_fb):
+// the backward pass starts at pts_out[i] - (start_i - pts_in[i]), the same prior
+// in reverse; status and fb_err as in the fb overload above.
+inline void calcOpticalFlowPyrLK(const amd::ImageView& prev, const amd::ImageView& next,
+                                 const std::vector<Point2f>& pts_in, const std::vector<Point2f>& initial_flow,
+                                 std::vector<Point2f>& pts_out, std::vector<uint8_t>& status,
+                                 std::vector<float>& fb_err, double fb_max,
+                                 amd::Context& ctx = amd::Context::thread_default()) {
+  if (prev.rows != next.rows || prev.cols != next.cols || prev.step != next.step)
+    throw std::invalid_argument("calcOpticalFlowPyrLK: images differ in shape");
+  if (initial_flow.size() != pts_in.size())
+    throw std::invalid_argument("calcOpticalFlowPyrLK: initial_flow holds one point per feature");
+  if (!(fb_max > 0.0)) throw std::invalid_argument("calcOpticalFlowPyrLK: fb_max must be > 0");
+  pts_out.resize(pts_in.size());
+  status.assign(pts_in.size(), 0);
+  fb_err.assign(pts_in.size(), 0.f);
+  if (pts_in.empty()) return;
+  me_klt_params kp;
+  me_klt_default_params(&kp);
+  ctx.check(me_klt_track_guided_fb(ctx.get(), ME_HOST, prev.data, next.data, prev.cols, prev.rows, prev.step,
+                                   &pts_in[0].x, &initial_flow[0].x, &pts_out[0].x, status.data(), fb_err.data(),
+                                   (int)pts_in.size(), &kp, fb_max),
+            "calcOpticalFlowPyrLK");
+}
+
 // Corner response of an 8-bit image (A12b, no reference counterpart: the
 // application's feature detector): rows x cols doubles, the KLT's minimum
 // eigenvalue of the win x win window centred on each pixel, 0 where the KLT
@@ -888,6 +936,13 @@ class WindowedStereoVO {
   // Before the first process(); a negative or NaN bound, or a later call, throws.
   void setMatchLrMax(double lrMax) {
     check(me_vo_loop_set_match_lr(v_.get(), lrMax), "WindowedStereoVO::setMatchLrMax");
+  }
+  // Guided tracking (me_hip.h A12f, me_vo_loop_set_klt_predict): on = the
+  // tracker starts each feature at its landmark's pixel under the predicted
+  // pose; off (the default) at the feature's old position.  Before the first
+  // process(); a later call throws.
+  void setKltPredict(bool on) {
+    check(me_vo_loop_set_klt_predict(v_.get(), on ? 1 : 0), "WindowedStereoVO::setKltPredict");
   }
   // Rectification inside the loop (me_hip.h A12d, me_vo_loop_set_rectify): with
   // the two camera models (R = the R1 / R2 of the stereo calibration) process()

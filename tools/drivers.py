@@ -18,6 +18,11 @@ loads another build of libme_hip.so (tools/build_variant.sh).
   klt_fb [--reps --repeats --check --loop N]
                          me_klt_track_fb beside me_klt_track on the config-3 frame (2000 features), alternating
                          in one process, and the config-3 native loop with klt_fb_max 0 / 0.5, alternating
+  klt_guided [--reps --repeats --check --guess G --loop N --fast N]
+                         me_klt_track_guided beside me_klt_track on the config-3 frame (2000 features; the guess is
+                         the unguided result moved by up to 2 px), alternating in one process, the config-3
+                         native loop with klt_predict off / on, alternating, and (--fast N, CPU only, no
+                         device touched) the oracle-backend loop off / on over every 6th keyframe of the arc
   match_lr [--reps --repeats --check --loop N --plain-only]
                          me_mi_epipolar_match_lr beside me_mi_epipolar_match on a config-3 stereo pair (2000
                          tracked-form and 250 new-form features), alternating in one process, and the config-3
@@ -581,6 +586,168 @@ def cmd_klt_fb(a):
     print(json.dumps(out))
 
 
+def _fast_sequence_cpu(n):
+    """The oracle-backend loop (CPU) with klt_predict off and on over a fast
+    sequence: every 6th pose of the arc (3 m and 1.8 deg per keyframe) rendered
+    at config-1 size; mean tracked features and the final centre drift."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from pipeline_oracle import OracleBackend  # checker only
+
+    from uasl_motion_estimation_amd import pipeline as PL
+    from uasl_motion_estimation_amd import synthetic as S
+    c = 1
+    cfg0 = S.CONFIGS[c]
+    W, H = cfg0["width"], cfg0["height"]
+    K = S.intrinsics(W, H)
+    scene = S.CorridorScene(S.SEED0 + c, S.arc_radius())
+    arc = S.trajectory_arc(6 * n)[::6]
+    truth = [np.concatenate([t, S.R_to_aa_robust(R)]) for (R, t) in arc]
+    lut = S.tone_map()
+    frames = [(S.render_corridor(scene, K, R, t, W, H, 0.0), lut[S.render_corridor(scene, K, R, t, W, H, S.BASELINE)])
+              for (R, t) in arc]
+    runs = []
+    for on in (False, True):
+        cfg = PL.PipelineConfig.from_config(c, klt_predict=on)
+        vo = PL.WindowedStereoVO(cfg, OracleBackend(), K, truth[0], truth[1] - truth[0])
+        for t in range(n):
+            vo.process(t, *frames[t])
+        vo.finish()
+        drift = float(np.linalg.norm(PL.camera_centre(vo.poses[n - 1]) - PL.camera_centre(truth[n - 1])))
+        r = {"cpu_oracle_backend": True, "klt_predict": on, "keyframes": n,
+             "tracked_mean": round(float(np.mean([q.n_tracked for q in vo.results[1:]])), 1),
+             "tracked": [q.n_tracked for q in vo.results], "final_centre_drift_m": round(drift, 4)}
+        runs.append(r)
+        print(json.dumps(r), flush=True)
+    return runs
+
+
+def cmd_klt_guided(a):
+    """The guided tracker (csrc/klt.hip, me_klt_track_guided) beside the plain
+    one on cmd_klt's inputs, the guess being the unguided result moved by the
+    +-2 px pattern of tests/klt_guided_cases.py: ME_KT_KLT and ME_KT_PYR
+    events per call, --repeats blocks of --reps calls each, the two entry
+    points alternating.  Then (--loop N) the native VO loop at config 3 over N
+    corridor keyframes with klt_predict off and on, alternating, two repeats
+    each.  --fast N alone (no device touched) runs the CPU comparison of
+    _fast_sequence_cpu."""
+    if a.fast > 0:
+        print(json.dumps({"fast_sequence_cpu": _fast_sequence_cpu(a.fast)}))
+        return
+    import torch
+
+    from uasl_motion_estimation_amd import klt_ref as KR
+    from uasl_motion_estimation_amd import pipeline as PL
+    from uasl_motion_estimation_amd import synthetic as S
+    from uasl_motion_estimation_amd._lib import ME_DEVICE
+    from uasl_motion_estimation_amd.klt import klt_params
+    ctx = _setup(a.lib)
+    V = ctypes.c_void_p
+    W, H, N = 1280, 720, 2000
+    scene, K, stream = S.stereo_stream(20261018, W, H, 2)
+    pts = S.grid_features(np.random.default_rng(0), N, W, H, 12).astype(np.float32)
+    dp, dn, din, dg, dout, dst = (ctx.malloc(W * H), ctx.malloc(W * H), ctx.malloc(8 * N), ctx.malloc(8 * N),
+                                  ctx.malloc(8 * N), ctx.malloc(N))
+    L0, L1 = np.ascontiguousarray(stream[0].left), np.ascontiguousarray(stream[1].left)
+    ctx.h2d(dp, L0)
+    ctx.h2d(dn, L1)
+    ctx.h2d(din, pts)
+    kp = klt_params()
+
+    def plain():
+        ctx.check(ctx.lib.me_klt_track(ctx.h, ME_DEVICE, V(dp), V(dn), W, H, W, V(din), V(dout), V(dst), N,
+                                       ctypes.byref(kp)), "me_klt_track")
+
+    def guided():
+        ctx.check(ctx.lib.me_klt_track_guided(ctx.h, ME_DEVICE, V(dp), V(dn), W, H, W, V(din), V(dg), V(dout), V(dst),
+                                              N, ctypes.byref(kp)), "me_klt_track_guided")
+    plain()
+    ctx.synchronize()
+    unguided, ust = np.zeros((N, 2), np.float32), np.zeros(N, np.uint8)
+    ctx.d2h(unguided, dout)
+    ctx.d2h(ust, dst)
+    k = np.arange(N)
+    if a.guess == "pts":  # the plain tracker's own start: the guided instance doing the plain one's work
+        guess = pts.copy()
+    else:
+        e = np.stack([((7 * k) % 9 - 4) / 2.0, ((5 * k) % 9 - 4) / 2.0], -1)
+        guess = (unguided.astype(np.float64) + (e if a.guess == "result2px" else 0.0)).astype(np.float32)
+    ctx.h2d(dg, guess)
+    out = {"inputs": f"{W}x{H}, {N} features, guess = {a.guess}", "reps": a.reps, "calls": []}
+    for fn in (plain, guided):
+        for _ in range(5):
+            fn()
+    ctx.synchronize()
+    for rep_ in range(a.repeats):
+        for name, fn in (("me_klt_track", plain), ("me_klt_track_guided", guided)):
+            ctx.timing_reset()
+            ctx.timing(True, ["KLT", "PYR"])
+            w0 = time.perf_counter()
+            for _ in range(a.reps):
+                fn()
+            ctx.synchronize()
+            wall = (time.perf_counter() - w0) / a.reps * 1e6
+            ctx.timing(False)
+            r = {"call": name, "repeat": rep_, "wall_us_per_call": round(wall, 2)}
+            for fam in ("PYR", "KLT"):
+                cnt, ms = ctx.timing_read(fam)
+                r[f"{fam}_us_per_call"] = round(1000 * ms / max(cnt, 1), 2)
+                r[f"{fam}_timed"] = cnt
+            out["calls"].append(r)
+            print(json.dumps(r), flush=True)
+    got, gst = np.zeros((N, 2), np.float32), np.zeros(N, np.uint8)
+    ctx.d2h(got, dout)
+    ctx.d2h(gst, dst)
+    out["tracked_unguided"], out["tracked_guided"] = int(ust.sum()), int(gst.sum())
+    both = (ust == 1) & (gst == 1)
+    out["max_px_between_guided_and_unguided"] = round(float(np.abs(got[both] - unguided[both]).max()), 4)
+    if a.check:
+        ref, rst = KR.klt_track_ref(L0, L1, pts, guess)
+        same = np.array_equal(got.view(np.uint32), ref.view(np.uint32)) and np.array_equal(gst, rst)
+        print(f"klt_guided parity vs the restatement: {'bit-exact' if same else 'MISMATCH'} (tracked: unguided "
+              f"{out['tracked_unguided']}, guided {out['tracked_guided']} of {N})", flush=True)
+        if not same:
+            sys.exit(1)
+    for d in (dp, dn, din, dg, dout, dst):
+        ctx.free(d)
+    if a.loop > 0:
+        c, NK = 3, a.loop
+        arc = S.trajectory_arc(max(NK, 2))
+        truth = [np.concatenate([t, S.R_to_aa_robust(R)]) for (R, t) in arc]
+        K = S.intrinsics(1280, 720)
+        frames = []
+        for c0 in range(0, NK, 50):
+            _, fr = S.corridor_frames_torch(S.SEED0 + c, 1280, 720, c0, min(50, NK - c0))
+            frames += [(Lk.contiguous(), Rk.contiguous()) for (Lk, Rk, _, _) in fr]
+            torch.cuda.synchronize()
+            print(f"rendered {len(frames)} keyframes", flush=True)
+        runs = []
+        for rep_ in range(-1, 2):  # (-1: a short untimed run, the first loop of a process pays the allocations)
+            for on in (False, True):
+                cfg = PL.PipelineConfig.from_config(c, klt_predict=on)
+                vo = PL.NativeStereoVO(cfg, ctx, K, truth[0], truth[1] - truth[0], log_events=False, overlap=True)
+                t0 = time.perf_counter()
+                for t in range(NK if rep_ >= 0 else min(NK, 30)):
+                    vo.process(t, *frames[t])
+                vo.finish()
+                dt = time.perf_counter() - t0
+                if rep_ < 0:
+                    vo.close()
+                    continue
+                st = vo._stats()
+                res = vo.results
+                vo.close()
+                names = ["klt_match", "first_match", "scale_submit", "window_submit", "ba_result", "scale_result"]
+                r = {"klt_predict": on, "repeat": rep_, "keyframes": NK, "keyframes_per_s": round(NK / dt, 2),
+                     "tracked_mean": round(float(np.mean([q.n_tracked for q in res[2:]])), 1),
+                     "new_mean": round(float(np.mean([q.n_new for q in res[2:]])), 1),
+                     "host_s": round(st[0], 4), "blocked_s": round(st[1], 4),
+                     "wait_ms_per_keyframe": {k: round(1e3 * st[3 + i] / NK, 4) for i, k in enumerate(names)}}
+                runs.append(r)
+                print(json.dumps(r), flush=True)
+        out["loop_config3"] = runs
+    print(json.dumps(out))
+
+
 def cmd_match_lr(a):
     """The left-right check (csrc/mi.hip, me_mi_epipolar_match_lr) beside the
     plain matcher on a config-3 stereo pair, in the loop's two forms: 2000
@@ -1040,6 +1207,15 @@ def main():
     p.add_argument("--fb-max", dest="fb_max", type=float, default=0.5)
     p.add_argument("--check", type=int, default=1)
     p.add_argument("--loop", type=int, default=200, help="keyframes of the config-3 native loop per run (0: skip)")
+    p = sub.add_parser("klt_guided")
+    p.add_argument("--reps", type=int, default=200)
+    p.add_argument("--repeats", type=int, default=3)
+    p.add_argument("--check", type=int, default=1)
+    p.add_argument("--loop", type=int, default=200, help="keyframes of the config-3 native loop per run (0: skip)")
+    p.add_argument("--guess", choices=("result2px", "result", "pts"), default="result2px",
+                   help="the guess: the unguided result moved by up to 2 px, the unguided result, or pts_in")
+    p.add_argument("--fast", type=int, default=0,
+                   help="> 0: only the CPU comparison on every 6th keyframe of the arc, this many keyframes")
     p = sub.add_parser("match_lr")
     p.add_argument("--reps", type=int, default=200)
     p.add_argument("--repeats", type=int, default=3)

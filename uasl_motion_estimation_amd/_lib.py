@@ -184,7 +184,7 @@ EXPORTS = [
     "me_vo_ba_chain", "me_vo_window_submit",
     "me_comm_unique_id", "me_comm_create_rccl", "me_comm_create_callback", "me_comm_destroy", "me_comm_info",
     "me_comm_allreduce", "me_comm_calibrate", "me_comm_exchange_us", "me_ba_shard_worthwhile_comm", "me_ba_solve_comm", "me_ba_shard_worthwhile", "me_ba_shard_exchange_us",
-    "me_klt_default_params", "me_klt_track", "me_klt_track_fb",
+    "me_klt_default_params", "me_klt_track", "me_klt_track_fb", "me_klt_track_guided", "me_klt_track_guided_fb",
     "me_corner_default_params", "me_corner_response", "me_vo_new_corners",
     "me_rectify_map", "me_remap_tile_dims", "me_remap_q5", "me_vo_loop_set_rectify",
     "me_clahe_default_params", "me_clahe", "me_clahe_apply_rows", "me_vo_loop_set_equalise",
@@ -194,6 +194,7 @@ EXPORTS = [
     "me_vo_loop_default_config", "me_vo_loop_create", "me_vo_loop_destroy", "me_vo_loop_last_error",
     "me_vo_loop_process", "me_vo_loop_finish", "me_vo_loop_results", "me_vo_loop_events", "me_vo_loop_tracks",
     "me_vo_loop_poses", "me_vo_loop_frame_obs", "me_vo_loop_frames", "me_vo_loop_stats", "me_vo_loop_set_match_lr",
+    "me_vo_loop_set_klt_predict",
 ]
 
 class MonoParamsC(ctypes.Structure):
@@ -322,6 +323,7 @@ def load_library(path: str | None = None):
         "me_vo_loop_create": (c_int, [c_void_p, c_void_p, P(VOLoopConfigC), P(c_void_p)]),
         "me_vo_loop_destroy": (None, [c_void_p]),
         "me_vo_loop_set_match_lr": (c_int, [c_void_p, c_double]),
+        "me_vo_loop_set_klt_predict": (c_int, [c_void_p, c_int]),
         "me_vo_loop_last_error": (ctypes.c_char_p, [c_void_p]),
         "me_vo_loop_process": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int]),
         "me_vo_loop_finish": (c_int, [c_void_p]),
@@ -337,6 +339,10 @@ def load_library(path: str | None = None):
                                  c_void_p, c_int, P(KLTParamsC)]),
         "me_klt_track_fb": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                     c_void_p, c_void_p, c_int, P(KLTParamsC), c_double]),
+        "me_klt_track_guided": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                        c_void_p, c_void_p, c_int, P(KLTParamsC)]),
+        "me_klt_track_guided_fb": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_int, P(KLTParamsC), c_double]),
         "me_corner_default_params": (None, [P(CornerParamsC)]),
         "me_corner_response": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, P(CornerParamsC), c_void_p]),
         "me_vo_new_corners": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,

@@ -16,6 +16,9 @@
 // me_klt_track_fb (me_hip.h A12c) is the forward-backward check on the same
 // kernels: derivatives of the next pyramid too, a second klt_kernel launch on
 // the pyramid view with the two images swapped, and a per-feature gate.
+// me_klt_track_guided / me_klt_track_guided_fb (me_hip.h A12f) are the same
+// launches on the guided instances of klt_kernel: the top level's search
+// starts at a per-feature guess instead of at the feature's old position.
 #include <algorithm>
 #include <cstring>
 #include <vector>
@@ -228,10 +231,20 @@ __device__ __forceinline__ void stage_region(uint32_t* reg, const uint8_t* __res
 // 0, or whose start lies outside the level-0 image (the tracker then reports
 // status 0 whatever it computes), is not tracked: status 0, pout = pin.  The
 // test is wave-uniform and the plain instance compiles without it.
-template <bool kGated>
+//
+// kGuided (me_klt_track_guided, me_hip.h A12f): the search of the top pyramid
+// level starts at the feature's guess when that lies inside the level-0 image
+// (both comparisons are false for NaN), at the feature's own position
+// otherwise; the template and everything below the start are the plain
+// tracker's.  The guess is read and tested like the position it replaces:
+// uniform address, scalar registers.  With bguess given, lane 0 also writes
+// the backward pass's guess, q - (s - pin) in float32 (two roundings).  The
+// instances without a guess compile without any of it.
+template <bool kGated, bool kGuided>
 __global__ __launch_bounds__(256) void klt_kernel(Pyr P, const float* __restrict__ pin, float* __restrict__ pout,
                                                   uint8_t* __restrict__ status, int n, int win, int max_iters,
-                                                  double eps2, double min_eig, const uint8_t* __restrict__ gate) {
+                                                  double eps2, double min_eig, const uint8_t* __restrict__ gate,
+                                                  const float* __restrict__ guess, float* __restrict__ bguess) {
   __shared__ __attribute__((aligned(16))) uint32_t regions[4][kRegion * kRegion];
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (scalar: the feature, its region and
@@ -268,13 +281,21 @@ __global__ __launch_bounds__(256) void klt_kernel(Pyr P, const float* __restrict
     asm volatile("" : "+v"(roff[q]));  // kept in a register: one add per tap address in the LK loop
   }
   const float px0 = pin[2 * f], py0 = pin[2 * f + 1];
+  float sx0 = px0, sy0 = py0;  // where the top level's search starts
+  if constexpr (kGuided) {
+    const float ux = guess[2 * f], uy = guess[2 * f + 1];
+    if (ux >= 0.f && ux < (float)P.w[0] && uy >= 0.f && uy < (float)P.h[0]) {  // (wave-uniform; false for NaN)
+      sx0 = ux;
+      sy0 = uy;
+    }
+  }
   for (int L = P.nl - 1; L >= 0; --L) {
     const int W = P.w[L], H = P.h[L], SI = P.is[L];
     const float sc = 1.0f / (float)(1 << L);
     const float px = px0 * sc, py = py0 * sc;
     if (L == P.nl - 1) {
-      nx = px;
-      ny = py;
+      nx = kGuided ? sx0 * sc : px;
+      ny = kGuided ? sy0 * sc : py;
     } else {
       nx = nx * 2.0f;
       ny = ny * 2.0f;
@@ -446,6 +467,13 @@ __global__ __launch_bounds__(256) void klt_kernel(Pyr P, const float* __restrict
     pout[2 * f] = nx;
     pout[2 * f + 1] = ny;
     status[f] = st;
+    if constexpr (kGuided) {
+      if (bguess) {
+        const float ex = sx0 - px0, ey = sy0 - py0;
+        bguess[2 * f] = nx - ex;
+        bguess[2 * f + 1] = ny - ey;
+      }
+    }
   }
 }
 
@@ -546,12 +574,14 @@ __global__ void klt_fb_gate_kernel(const float* __restrict__ pin, const float* _
   if (fb_err) fb_err[i] = both ? (float)__dsqrt_rn(d2) : __builtin_inff();
 }
 
-// me_klt_track (fb = false) and me_klt_track_fb: argument checks, staging of
-// host-mode arguments, pyramids, kernels.
+// me_klt_track (fb = false) and me_klt_track_fb, and their guided forms
+// (guided = true: `guess` holds n x 2 floats in `mem`): argument checks,
+// staging of host-mode arguments, pyramids, kernels.
 int klt_run(me_ctx* c, const char* who, me_mem mem, const uint8_t* prev, const uint8_t* next, int w, int h, int stride,
-            const float* pin, float* pout, uint8_t* status, float* fb_err, int n, const me_klt_params* kp, bool fb,
-            double fb_max) {
+            const float* pin, const float* guess, float* pout, uint8_t* status, float* fb_err, int n,
+            const me_klt_params* kp, bool fb, double fb_max, bool guided) {
   if (!c || !kp) return ME_ERR_INVALID;
+  if (guided) ME_CHECK(c, guess != nullptr, "%s: guess is NULL", who);
   ME_CHECK(c, w > 0 && h > 0 && stride >= w && n >= 0, "%s: bad image", who);
   ME_CHECK(c, kp->win >= 3 && (kp->win & 1) && kp->win * kp->win <= 64 * kMaxWinPx,
            "%s: window must be odd and <= 21", who);
@@ -568,13 +598,23 @@ int klt_run(me_ctx* c, const char* who, me_mem mem, const uint8_t* prev, const u
   // fb: the backward result and the two passes' status bytes
   float* dback = nullptr;
   uint8_t *dsf = nullptr, *dsb = nullptr;
+  // guided: the guess (host mode) and, with fb, the backward pass's guess lead the block, 8 bytes per feature each
+  const float* dguess = guess;
+  float* dbguess = nullptr;
+  const size_t lead = guided ? ((mem == ME_HOST ? 8 : 0) + (fb ? 8 : 0)) * m : 0;
   if (mem == ME_HOST) {
     void *a, *b, *pts;
     size_t bytes = (size_t)stride * (h - 1) + w;
     ME_TRY(me_scratch(c, SLOT_IMG_L, bytes, &a));
     ME_TRY(me_scratch(c, SLOT_IMG_R, bytes, &b));
     // pin 8 | pout 8 | status 1 per feature; fb: | backward 8 | fb_err 4 | sf 1 | sb 1
-    ME_TRY(me_scratch(c, SLOT_KLT_PTS, (fb ? 31 : 17) * m + 64, &pts));
+    ME_TRY(me_scratch(c, SLOT_KLT_PTS, lead + (fb ? 31 : 17) * m + 64, &pts));
+    if (guided) {
+      dguess = (const float*)pts;
+      if (fb) dbguess = (float*)pts + 2 * m;
+      pts = (char*)pts + lead;
+      if (n) ME_HIP(c, hipMemcpyAsync((void*)dguess, guess, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    }
     ME_HIP(c, hipMemcpyAsync(a, prev, bytes, hipMemcpyHostToDevice, c->stream));
     ME_HIP(c, hipMemcpyAsync(b, next, bytes, hipMemcpyHostToDevice, c->stream));
     dprev = (const uint8_t*)a;
@@ -593,7 +633,9 @@ int klt_run(me_ctx* c, const char* who, me_mem mem, const uint8_t* prev, const u
     if (n) ME_HIP(c, hipMemcpyAsync((void*)dpin, pin, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));
   } else if (fb) {
     void* pts;
-    ME_TRY(me_scratch(c, SLOT_KLT_PTS, 10 * m + 64, &pts));
+    ME_TRY(me_scratch(c, SLOT_KLT_PTS, lead + 10 * m + 64, &pts));
+    if (guided) dbguess = (float*)pts;
+    pts = (char*)pts + lead;
     dback = (float*)pts;
     dsf = (uint8_t*)(dback + 2 * m);
     dsb = dsf + m;
@@ -604,14 +646,20 @@ int klt_run(me_ctx* c, const char* who, me_mem mem, const uint8_t* prev, const u
     me_ktimer t(c, ME_KT_KLT);
     const dim3 grd((n + 3) / 4), blk(256);
     const double eps2 = kp->eps * kp->eps;
+    // the guided instances take the guess; with fb the forward pass also writes the backward pass's guess
+    // (bguess = q - (s - pin)), which the gated instance then starts from
+    const auto fwd = guided ? klt_kernel<false, true> : klt_kernel<false, false>;
+    const auto bwd = guided ? klt_kernel<true, true> : klt_kernel<true, false>;
+    const uint8_t* no_gate = nullptr;
+    float* no_bguess = nullptr;
     if (!fb) {
-      hipLaunchKernelGGL(klt_kernel<false>, grd, blk, 0, c->stream, P, dpin, dpout, dst, n, kp->win, kp->max_iters,
-                         eps2, kp->min_eig, (const uint8_t*)nullptr);
+      hipLaunchKernelGGL(fwd, grd, blk, 0, c->stream, P, dpin, dpout, dst, n, kp->win, kp->max_iters, eps2,
+                         kp->min_eig, no_gate, dguess, no_bguess);
     } else {
-      hipLaunchKernelGGL(klt_kernel<false>, grd, blk, 0, c->stream, P, dpin, dpout, dsf, n, kp->win, kp->max_iters,
-                         eps2, kp->min_eig, (const uint8_t*)nullptr);
-      hipLaunchKernelGGL(klt_kernel<true>, grd, blk, 0, c->stream, B, (const float*)dpout, dback, dsb, n, kp->win,
-                         kp->max_iters, eps2, kp->min_eig, (const uint8_t*)dsf);
+      hipLaunchKernelGGL(fwd, grd, blk, 0, c->stream, P, dpin, dpout, dsf, n, kp->win, kp->max_iters, eps2,
+                         kp->min_eig, no_gate, dguess, dbguess);
+      hipLaunchKernelGGL(bwd, grd, blk, 0, c->stream, B, (const float*)dpout, dback, dsb, n, kp->win, kp->max_iters,
+                         eps2, kp->min_eig, (const uint8_t*)dsf, (const float*)dbguess, no_bguess);
       hipLaunchKernelGGL(klt_fb_gate_kernel, dim3((n + 255) / 256), blk, 0, c->stream, dpin, (const float*)dback,
                          (const uint8_t*)dsf, (const uint8_t*)dsb, dst, derr, n, fb_max * fb_max);
     }
@@ -634,12 +682,30 @@ extern "C" int me_klt_track(me_ctx* c, me_mem mem, const uint8_t* prev, const ui
                             int stride, const float* pin, float* pout, uint8_t* status, int n,
                             const me_klt_params* kp) {
   me_range range_("me_klt_track");
-  return klt_run(c, "me_klt_track", mem, prev, next, w, h, stride, pin, pout, status, nullptr, n, kp, false, 0.0);
+  return klt_run(c, "me_klt_track", mem, prev, next, w, h, stride, pin, nullptr, pout, status, nullptr, n, kp, false,
+                 0.0, false);
 }
 
 extern "C" int me_klt_track_fb(me_ctx* c, me_mem mem, const uint8_t* prev, const uint8_t* next, int w, int h,
                                int stride, const float* pin, float* pout, uint8_t* status, float* fb_err, int n,
                                const me_klt_params* kp, double fb_max) {
   me_range range_("me_klt_track_fb");
-  return klt_run(c, "me_klt_track_fb", mem, prev, next, w, h, stride, pin, pout, status, fb_err, n, kp, true, fb_max);
+  return klt_run(c, "me_klt_track_fb", mem, prev, next, w, h, stride, pin, nullptr, pout, status, fb_err, n, kp, true,
+                 fb_max, false);
+}
+
+extern "C" int me_klt_track_guided(me_ctx* c, me_mem mem, const uint8_t* prev, const uint8_t* next, int w, int h,
+                                   int stride, const float* pin, const float* guess, float* pout, uint8_t* status,
+                                   int n, const me_klt_params* kp) {
+  me_range range_("me_klt_track_guided");
+  return klt_run(c, "me_klt_track_guided", mem, prev, next, w, h, stride, pin, guess, pout, status, nullptr, n, kp,
+                 false, 0.0, true);
+}
+
+extern "C" int me_klt_track_guided_fb(me_ctx* c, me_mem mem, const uint8_t* prev, const uint8_t* next, int w, int h,
+                                      int stride, const float* pin, const float* guess, float* pout, uint8_t* status,
+                                      float* fb_err, int n, const me_klt_params* kp, double fb_max) {
+  me_range range_("me_klt_track_guided_fb");
+  return klt_run(c, "me_klt_track_guided_fb", mem, prev, next, w, h, stride, pin, guess, pout, status, fb_err, n, kp,
+                 true, fb_max, true);
 }

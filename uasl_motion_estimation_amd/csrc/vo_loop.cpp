@@ -207,6 +207,7 @@ struct me_vo_loop {
   me_vo_loop_config cfg{};
   double match_lr = 0.0;  // > 0: every matcher call takes its _lr form with this bound (me_vo_loop_set_match_lr)
   std::string err;
+  bool klt_predict = false;  // the tracker starts at each landmark's predicted pixel (me_vo_loop_set_klt_predict)
   double f = 0, cx = 0, cy = 0;
   int nx = 1, ny = 1;
   double cw = 1, ch = 1;
@@ -618,16 +619,32 @@ struct me_vo_loop {
   }
 
   // ---- front end
-  int klt_submit(const Imgs& prev, const Imgs& cur, const std::vector<float>& pts) {
+  // guess (klt_predict): the features' predicted pixels, uploaded behind them in the same copy
+  int klt_submit(const Imgs& prev, const Imgs& cur, const std::vector<float>& pts, const std::vector<float>* guess) {
     const int n = (int)pts.size() / 2;
+    const size_t in_bytes = (guess ? 16 : 8) * (size_t)n;
     void *hp, *d_in, *dres;
-    VL_TRY(hbuf("klt_in", 8 * (size_t)n, &hp), "klt");
+    VL_TRY(hbuf("klt_in", in_bytes, &hp), "klt");
     std::memcpy(hp, pts.data(), 8 * (size_t)n);
-    VL_TRY(dbuf("klt_in", 8 * (size_t)n, &d_in), "klt");
+    if (guess) std::memcpy((char*)hp + 8 * (size_t)n, guess->data(), 8 * (size_t)n);
+    VL_TRY(dbuf("klt_in", in_bytes, &d_in), "klt");
     VL_TRY(dbuf("res", 14 * (size_t)n, &dres), "klt");
-    VL_TRY(me_memcpy_async(tctx, d_in, hp, 8 * (size_t)n), "klt H2D");
+    VL_TRY(me_memcpy_async(tctx, d_in, hp, in_bytes), "klt H2D");
     me_klt_params kp;
     me_klt_default_params(&kp);
+    if (guess) {
+      const float* d_guess = (const float*)d_in + 2 * (size_t)n;
+      if (cfg.klt_fb_max > 0.0)
+        VL_TRY(me_klt_track_guided_fb(tctx, ME_DEVICE, prev.L, cur.L, cfg.width, cfg.height, cfg.width,
+                                      (const float*)d_in, d_guess, (float*)dres, (uint8_t*)dres + 12 * (size_t)n,
+                                      nullptr, n, &kp, cfg.klt_fb_max),
+               "me_klt_track_guided_fb");
+      else
+        VL_TRY(me_klt_track_guided(tctx, ME_DEVICE, prev.L, cur.L, cfg.width, cfg.height, cfg.width,
+                                   (const float*)d_in, d_guess, (float*)dres, (uint8_t*)dres + 12 * (size_t)n, n, &kp),
+               "me_klt_track_guided");
+      return ME_OK;
+    }
     if (cfg.klt_fb_max > 0.0)  // the forward-backward check: its combined status is the byte the matcher gates on
       VL_TRY(me_klt_track_fb(tctx, ME_DEVICE, prev.L, cur.L, cfg.width, cfg.height, cfg.width, (const float*)d_in,
                              (float*)dres, (uint8_t*)dres + 12 * (size_t)n, nullptr, n, &kp, cfg.klt_fb_max),
@@ -1193,7 +1210,23 @@ struct me_vo_loop {
         pts[2 * k] = po.feats[4 * pos];
         pts[2 * k + 1] = po.feats[4 * pos + 1];
       }
-      VL_TRY(klt_submit(imgs[prev_t], im, pts), "klt");
+      std::vector<float> guess;
+      if (klt_predict) {
+        // pose(t) ahead of step 3 (the pops in between change none of its inputs); pipeline.predict_uv
+        const Pose gp = predict_pose(t);
+        const Mat3 R = aa_to_R(&gp[3]);
+        guess.resize(2 * act.size());
+        for (size_t k = 0; k < act.size(); ++k) {
+          const double* Xk = &X[3 * act[k]];
+          const double Xc = (Xk[0] * R[0] + Xk[1] * R[1]) + Xk[2] * R[2] + gp[0];
+          const double Yc = (Xk[0] * R[3] + Xk[1] * R[4]) + Xk[2] * R[5] + gp[1];
+          const double Z = (Xk[0] * R[6] + Xk[1] * R[7] + Xk[2] * R[8]) + gp[2];
+          const float nan = std::numeric_limits<float>::quiet_NaN();
+          guess[2 * k] = Z > 0 ? (float)(f * Xc / Z + cx) : nan;
+          guess[2 * k + 1] = Z > 0 ? (float)(f * Yc / Z + cy) : nan;
+        }
+      }
+      VL_TRY(klt_submit(imgs[prev_t], im, pts, klt_predict ? &guess : nullptr), "klt");
     }
     // 2. pops of frame t-1's completion
     if (has_pending) pop(pending.t + 1 - cfg.window);
@@ -1456,6 +1489,20 @@ int me_vo_loop_set_match_lr(me_vo_loop* v, double lr_max) {
     return ME_ERR_STATE;
   }
   v->match_lr = lr_max;
+  return ME_OK;
+}
+
+int me_vo_loop_set_klt_predict(me_vo_loop* v, int on) {
+  if (!v) return ME_ERR_INVALID;
+  if (on != 0 && on != 1) {
+    v->err = "me_vo_loop_set_klt_predict: on must be 0 or 1";
+    return ME_ERR_INVALID;
+  }
+  if (v->has_prev || v->failed) {
+    v->err = "me_vo_loop_set_klt_predict: guided tracking is set before the first me_vo_loop_process";
+    return ME_ERR_STATE;
+  }
+  v->klt_predict = on == 1;
   return ME_OK;
 }
 

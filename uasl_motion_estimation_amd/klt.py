@@ -9,6 +9,10 @@ With fb_max set the call is the forward-backward check (me_klt_track_fb,
 include/me_hip.h A12c): prev -> next, back next -> prev from the result, and a
 feature keeps status 1 only if both passes tracked it and it returns within
 fb_max pixels of where it started.
+
+With guess (n, 2) the search starts at each feature's guess instead of at its
+old position (me_klt_track_guided / me_klt_track_guided_fb, include/me_hip.h
+A12f); a guess that is not finite or lies outside the image is ignored.
 """
 from __future__ import annotations
 
@@ -25,10 +29,11 @@ def klt_params(win=21, max_level=3, max_iters=30, eps=0.01, min_eig=1e-4) -> KLT
     return k
 
 
-def calcOpticalFlowPyrLK(prev, nxt, pts, ctx: Context | None = None, fb_max: float | None = None, **kw):
+def calcOpticalFlowPyrLK(prev, nxt, pts, ctx: Context | None = None, fb_max: float | None = None, guess=None, **kw):
     """Track pts (n, 2) float32 from prev to nxt.  Returns (pts_out (n,2), status (n,) uint8); with fb_max
     (pixels, > 0) the status is the forward-backward check's and the return value is (pts_out, status,
-    fb_err (n,) float32: the round-trip distance, inf where a pass failed)."""
+    fb_err (n,) float32: the round-trip distance, inf where a pass failed).  guess (n, 2) float32: where each
+    feature's search starts in nxt (level-0 pixels); None: at the feature's position in prev."""
     ctx = ctx or default_context()
     prev = np.ascontiguousarray(prev, np.uint8)
     nxt = np.ascontiguousarray(nxt, np.uint8)
@@ -39,6 +44,19 @@ def calcOpticalFlowPyrLK(prev, nxt, pts, ctx: Context | None = None, fb_max: flo
     out = np.zeros_like(pts)
     st = np.zeros(len(pts), np.uint8)
     kp = klt_params(**kw)
+    if guess is not None:
+        guess = np.ascontiguousarray(guess, np.float32).reshape(-1, 2)
+        if guess.shape != pts.shape:
+            raise ValueError("guess must hold one (x, y) per feature")
+        if fb_max is not None:
+            err = np.zeros(len(pts), np.float32)
+            ctx.check(ctx.lib.me_klt_track_guided_fb(ctx.h, ME_HOST, vptr(prev), vptr(nxt), w, h, w, vptr(pts),
+                                                     vptr(guess), vptr(out), vptr(st), vptr(err), len(pts),
+                                                     ctypes.byref(kp), float(fb_max)), "me_klt_track_guided_fb")
+            return out, st, err
+        ctx.check(ctx.lib.me_klt_track_guided(ctx.h, ME_HOST, vptr(prev), vptr(nxt), w, h, w, vptr(pts), vptr(guess),
+                                              vptr(out), vptr(st), len(pts), ctypes.byref(kp)), "me_klt_track_guided")
+        return out, st
     if fb_max is not None:
         err = np.zeros(len(pts), np.float32)
         ctx.check(ctx.lib.me_klt_track_fb(ctx.h, ME_HOST, vptr(prev), vptr(nxt), w, h, w, vptr(pts), vptr(out),

@@ -126,6 +126,7 @@ class PipelineConfig:
     corner_min_eig: float = 1e-4
     klt_fb_max: float = 0.0       # > 0: forward-backward check of the tracker, bound in pixels (klt_fb_host); 0: off
     match_lr_max: float = 0.0     # > 0: left-right check of the stereo matches, bound in pixels (match_lr_host); 0: off
+    klt_predict: bool = False     # True: the tracker starts at each landmark's predicted pixel (predict_uv, klt_ref.py)
     rectify: "StereoRectifier | None" = None  # rectify.StereoRectifier: process() takes raw images and warps them first
     equalise: "Clahe | None" = None  # equalise.Clahe: both images of a keyframe are equalised ahead of the tracker
 
@@ -334,6 +335,25 @@ def klt_fb_host(klt, prev, cur, pts, fb_max: float):
     return q, status, fb_err
 
 
+def predict_uv(X, pose, f, cx, cy) -> np.ndarray:
+    """Pixels (n, 2) float32 of the landmarks X (n, 3) seen from the {t,
+    angle-axis} world -> camera pose: the tracker's initial guess
+    (PipelineConfig.klt_predict).  FP64, elementwise, in the order the native
+    loop uses: Xc = (X0 R00 + X1 R01) + X2 R02 + t0, Yc likewise with row 1, Z
+    as WindowedStereoVO._predicted_disparity forms it; u = f Xc / Z + cx,
+    v = f Yc / Z + cy where Z > 0, NaN elsewhere."""
+    X = np.asarray(X, np.float64).reshape(-1, 3)
+    pose = np.asarray(pose, np.float64)
+    R = aa_to_R(pose[3:])
+    Xc = (X[:, 0] * R[0, 0] + X[:, 1] * R[0, 1]) + X[:, 2] * R[0, 2] + pose[0]
+    Yc = (X[:, 0] * R[1, 0] + X[:, 1] * R[1, 1]) + X[:, 2] * R[1, 2] + pose[1]
+    Z = X @ R[2] + pose[2]
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        u = np.where(Z > 0, f * Xc / Z + cx, np.nan)
+        v = np.where(Z > 0, f * Yc / Z + cy, np.nan)
+        return np.stack([u, v], -1).astype(np.float32)
+
+
 def new_cells(t: int, uv_good: np.ndarray, grid) -> np.ndarray:
     """New features of keyframe t: the good tracked features (uv_good) occupy
     their grid cell (trunc((u - MARGIN) / cw), trunc((v - MARGIN) / ch)),
@@ -375,6 +395,7 @@ class Backend:
     detector = ("grid", 21, 1e-4)  # (detector, corner_win, corner_min_eig) of the loop's configuration
     klt_fb_max = 0.0  # PipelineConfig.klt_fb_max of the loop's configuration (0: no forward-backward check)
     match_lr_max = 0.0  # PipelineConfig.match_lr_max of the loop's configuration (0: no left-right check)
+    klt_predict = False  # PipelineConfig.klt_predict of the loop's configuration (True: klt_submit gets a guess)
     rectifier = None  # PipelineConfig.rectify of the loop's configuration (None: the images come rectified)
     rectifies = False  # True: frame_images takes raw images and warps them itself (on the device)
     equaliser = None  # PipelineConfig.equalise of the loop's configuration (None: the images are used as they come)
@@ -438,14 +459,22 @@ class Backend:
         raise NotImplementedError
 
     # ---- staged forms
-    def klt_submit(self, prev, cur, pts):
+    def klt_submit(self, prev, cur, pts, guess=None):
+        if guess is not None:
+            return (prev, cur, np.ascontiguousarray(pts, np.float32), np.ascontiguousarray(guess, np.float32))
         return (prev, cur, np.ascontiguousarray(pts, np.float32))
 
     def klt_match(self, h, imgs, lo, nd, dvalid):
         """KLT of the submitted points, then the MI search (lo, nd, dvalid per
         point) of those that pass the KLT gate: (uv, status, xr, ok)."""
-        prev, cur, pts = h
-        if self.klt_fb_max > 0.0:
+        prev, cur, pts = h[:3]
+        if len(h) > 3:  # guided: the numpy restatement of the whole tracker on the host images
+            from . import klt_ref
+            if self.klt_fb_max > 0.0:
+                uv, st, _ = klt_ref.klt_guided_fb_ref(prev[3], cur[3], pts, h[3], self.klt_fb_max)
+            else:
+                uv, st = klt_ref.klt_track_ref(prev[3], cur[3], pts, h[3])
+        elif self.klt_fb_max > 0.0:
             uv, st, _ = klt_fb_host(self.klt, prev, cur, pts, self.klt_fb_max)
         else:
             uv, st = self.klt(prev, cur, pts)
@@ -784,7 +813,7 @@ class GPUBackend(Backend):
 
     # ---- staged calls
     # device result block of a KLT + match: uv (8n) | xr (4n) | status (n) | ok (n)
-    def klt_submit(self, prev, cur, pts):
+    def klt_submit(self, prev, cur, pts, guess=None):
         import ctypes
 
         from ._lib import ME_DEVICE
@@ -795,12 +824,27 @@ class GPUBackend(Backend):
             return (0, prev, cur)
         H, W = prev[2]
         c = self.tctx
-        hp = self._hbuf("klt_in", 8 * n)
+        nb = 8 * n if guess is None else 16 * n  # the guess rides behind the features in the same copy
+        hp = self._hbuf("klt_in", nb)
         self._view(hp, np.float32, 2 * n)[:] = np.asarray(pts, np.float32).ravel()
-        d_in = self._dbuf("klt_in", 8 * n)
+        if guess is not None:
+            self._view(hp, np.float32, 2 * n, 8 * n)[:] = np.asarray(guess, np.float32).ravel()
+        d_in = self._dbuf("klt_in", nb)
         dres = self._dbuf("res", 14 * n)
-        c.copy_async(d_in, hp, 8 * n)
+        c.copy_async(d_in, hp, nb)
         kp = klt_params()
+        if guess is not None:
+            V = ctypes.c_void_p
+            if self.klt_fb_max > 0.0:
+                c.check(c.lib.me_klt_track_guided_fb(c.h, ME_DEVICE, V(prev[0]), V(cur[0]), W, H, W, V(d_in),
+                                                     V(d_in + 8 * n), V(dres), V(dres + 12 * n), None, n,
+                                                     ctypes.byref(kp), float(self.klt_fb_max)),
+                        "me_klt_track_guided_fb")
+            else:
+                c.check(c.lib.me_klt_track_guided(c.h, ME_DEVICE, V(prev[0]), V(cur[0]), W, H, W, V(d_in),
+                                                  V(d_in + 8 * n), V(dres), V(dres + 12 * n), n, ctypes.byref(kp)),
+                        "me_klt_track_guided")
+            return (n, prev, cur)
         if self.klt_fb_max > 0.0:  # the combined status lands in the byte the matcher gates on
             c.check(c.lib.me_klt_track_fb(c.h, ME_DEVICE, ctypes.c_void_p(prev[0]), ctypes.c_void_p(cur[0]), W, H, W,
                                           ctypes.c_void_p(d_in), ctypes.c_void_p(dres),
@@ -1235,6 +1279,7 @@ class WindowedStereoVO:
         self.be.detector = (cfg.detector, cfg.corner_win, cfg.corner_min_eig)
         self.be.klt_fb_max = float(cfg.klt_fb_max)
         self.be.match_lr_max = float(cfg.match_lr_max)
+        self.be.klt_predict = bool(cfg.klt_predict)
         self.be.rectifier = cfg.rectify
         self.be.equaliser = cfg.equalise
         if hasattr(backend, "reserve"):
@@ -1388,7 +1433,8 @@ class WindowedStereoVO:
         and new tracks use the state after BA(t - 2) -- so BA(t - 1) runs on
         the device while the host tracks, matches and books keyframe t, and
         BA(t) is queued as soon as BA(t - 1) is applied:
-          1. KLT of the active tracks (L(t-1) -> L(t)) queued;
+          1. KLT of the active tracks (L(t-1) -> L(t)) queued (klt_predict: from
+             each landmark's pixel at step 3's pose, predicted here already);
           2. pops of keyframe t-1's completion (features leaving the window);
           3. pose(t) predicted (constant velocity, lagged state);
           4. KLT gate + MI matching of the tracked features, new features of
@@ -1417,7 +1463,13 @@ class WindowedStereoVO:
             aid = self.ids[act]
             # (the active tracks are exactly the features of keyframe t-1, in ID order, as a rule)
             pos = np.arange(len(pid)) if len(aid) == len(pid) and np.array_equal(aid, pid) else np.searchsorted(pid, aid)
-            kh = self.be.klt_submit(self.prev_imgs, imgs, np.ascontiguousarray(puv[pos, :2]))
+            if cfg.klt_predict:
+                # pose(t) ahead of step 3 (the pops in between change none of its inputs): each landmark's
+                # predicted pixel is where its search starts
+                guess = predict_uv(self.X[act], self._predict_pose(t), self.f, self.cx, self.cy)
+                kh = self.be.klt_submit(self.prev_imgs, imgs, np.ascontiguousarray(puv[pos, :2]), guess=guess)
+            else:
+                kh = self.be.klt_submit(self.prev_imgs, imgs, np.ascontiguousarray(puv[pos, :2]))
         # 2. pops of frame t-1's completion (active tracks keep their order)
         if self._pending is not None:
             self._pop(self._pending[0] + 1 - cfg.window)
@@ -1755,6 +1807,8 @@ class NativeStereoVO:
         # (a setter, not a configuration field: me_vo_loop_config keeps its layout)
         try:
             self._check(self.lib.me_vo_loop_set_match_lr(self.h, float(cfg.match_lr_max)), "me_vo_loop_set_match_lr")
+            if cfg.klt_predict:
+                self._check(self.lib.me_vo_loop_set_klt_predict(self.h, 1), "me_vo_loop_set_klt_predict")
             if cfg.rectify is not None:  # the loop builds the two maps itself, on its front context
                 cl, cr = cfg.rectify.left.to_c(), cfg.rectify.right.to_c()
                 self._check(self.lib.me_vo_loop_set_rectify(self.h, ctypes.byref(cl), ctypes.byref(cr),
