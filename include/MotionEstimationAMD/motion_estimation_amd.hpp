@@ -883,6 +883,30 @@ inline std::vector<uint8_t> clahe(const ImageView& img, int tilesX = 8, int tile
             "clahe");
   return out;
 }
+
+// A 16-bit image: `step` counts elements, not bytes.
+struct ImageView16 {
+  const uint16_t* data = nullptr;
+  int rows = 0, cols = 0;
+  int step = 0;  // elements per row
+  bool empty() const { return !data || rows <= 0 || cols <= 0; }
+};
+struct ToneMapParams {
+  int loPpm = 1000, hiPpm = 1000, minSpan = 256, alphaQ8 = 64;  // (a choice, not a measurement: me_hip.h A12g)
+  me_tonemap_params c() const { return me_tonemap_params{loPpm, hiPpm, minSpan, alphaQ8}; }
+};
+// 16 -> 8-bit tone map (A12g, no reference counterpart; build-defined and
+// integer-only, parity unpinned): one stateless me_tonemap16 on host memory.
+// Returns the 8-bit image, rows x cols bytes, dense.
+inline std::vector<uint8_t> tonemap16(const ImageView16& img, const ToneMapParams& params = ToneMapParams(),
+                                      Context& ctx = Context::thread_default()) {
+  if (img.empty()) throw std::invalid_argument("tonemap16: empty image");
+  const me_tonemap_params p = params.c();
+  std::vector<uint8_t> out((size_t)img.rows * img.cols);
+  ctx.check(me_tonemap16(ctx.get(), ME_HOST, img.data, img.cols, img.rows, img.step, out.data(), img.cols, &p, nullptr),
+            "tonemap16");
+  return out;
+}
 }  // namespace amd
 
 // The windowed stereo VO loop (me_vo_loop_*, csrc/vo_loop.hip): the
@@ -969,6 +993,33 @@ class WindowedStereoVO {
     check(me_vo_loop_set_equalise(v_.get(), &p), "WindowedStereoVO::setEqualise");
   }
   void clearEqualise() { check(me_vo_loop_set_equalise(v_.get(), nullptr), "WindowedStereoVO::clearEqualise"); }
+  // 16-bit ingest (me_hip.h A12g, me_vo_loop_set_tonemap): the loop takes
+  // 16-bit keyframes through process16() / process16Device() and reduces them
+  // to 8 bits on the front-end stream, each camera with a window state of its
+  // own, ahead of the warp and the equalisation.  Before the first keyframe;
+  // clearToneMap() switches it off again.  Bad parameters, or a later call, throw.
+  void setToneMap(const amd::ToneMapParams& params = amd::ToneMapParams()) {
+    const me_tonemap_params p = params.c();
+    check(me_vo_loop_set_tonemap(v_.get(), &p), "WindowedStereoVO::setToneMap");
+  }
+  void clearToneMap() { check(me_vo_loop_set_tonemap(v_.get(), nullptr), "WindowedStereoVO::clearToneMap"); }
+  // keyframe t as dense 16-bit host images (sizes as in process()); all keyframes
+  // of a loop come through the 16-bit entries or none
+  void process16(int t, const amd::ImageView16& left, const amd::ImageView16& right) {
+    if (left.empty() || right.empty() || left.step != left.cols || right.step != right.cols)
+      throw std::invalid_argument("WindowedStereoVO::process16: dense 16-bit images expected");
+    if (raw_[0]) {
+      if (left.cols != raw_[0] || left.rows != raw_[1] || right.cols != raw_[2] || right.rows != raw_[3])
+        throw std::invalid_argument("WindowedStereoVO::process16: raw images of the camera models' sizes expected");
+    } else if (left.rows != height_ || left.cols != width_ || right.rows != height_ || right.cols != width_)
+      throw std::invalid_argument("WindowedStereoVO::process16: images of the configured width x height expected");
+    check(me_vo_loop_process16(v_.get(), t, left.data, right.data, ME_HOST), "WindowedStereoVO::process16");
+  }
+  // keyframe t from device memory, dense 16-bit images: processDevice()'s rules
+  void process16Device(int t, const uint16_t* left, const uint16_t* right) {
+    if (!left || !right) throw std::invalid_argument("WindowedStereoVO::process16Device: null image");
+    check(me_vo_loop_process16(v_.get(), t, left, right, ME_DEVICE), "WindowedStereoVO::process16Device");
+  }
   // keyframe t (0, 1, 2, ...): host images of the configured size (of the
   // camera models' sizes after setRectification), copied in
   void process(int t, const amd::ImageView& left, const amd::ImageView& right) {

@@ -95,7 +95,7 @@ int me_host_free(me_ctx* ctx, void* hptr);
    stream, so time only the families a measurement needs. */
 enum { ME_KT_MI = 0, ME_KT_SCALE_RES = 1, ME_KT_SCALE_NEQ = 2, ME_KT_BA_LINEARIZE = 3, ME_KT_BA_POINTS = 4,
        ME_KT_BA_SCHUR = 5, ME_KT_BA_SOLVE = 6, ME_KT_BA_STEP = 7, ME_KT_KLT = 8, ME_KT_PYR = 9, ME_KT_NMS = 10,
-       ME_KT_CORNERS = 11, ME_KT_RECTIFY = 12, ME_KT_CLAHE = 13, ME_KT_COUNT = 16, ME_KT_ALL = 0xffff };
+       ME_KT_CORNERS = 11, ME_KT_RECTIFY = 12, ME_KT_CLAHE = 13, ME_KT_TONEMAP = 14, ME_KT_COUNT = 16, ME_KT_ALL = 0xffff };
 int me_timing_enable(me_ctx* ctx, int family_mask);
 int me_timing_read(me_ctx* ctx, int kernel, long* launches, double* total_ms);
 int me_timing_reset(me_ctx* ctx);
@@ -518,6 +518,26 @@ int me_vo_loop_set_equalise(me_vo_loop* v, const struct me_clahe_params* p /* NU
    ctx device, read during this call and the next one (keep it alive until
    me_vo_loop_process(t + 1) returns); ME_HOST: copied in. */
 int me_vo_loop_process(me_vo_loop* v, int t, const uint8_t* left, const uint8_t* right, me_mem mem);
+/* 16-bit ingest (A12g): with parameters the loop takes 16-bit keyframes
+   through me_vo_loop_process16 and reduces them to 8 bits itself.  Each camera
+   has a tone-map state of its own, created by the loop.  NULL switches it off
+   (the default: the loop makes exactly the calls it makes without this
+   setter).  Bad parameters (me_tonemap16's rules): ME_ERR_INVALID, and the
+   switch is left off; after the first process call: ME_ERR_STATE. */
+struct me_tonemap_params; /* defined in section A12g below */
+int me_vo_loop_set_tonemap(me_vo_loop* v, const struct me_tonemap_params* p /* NULL: off */);
+/* Keyframe t as 16-bit images: width x height of the loop (stride = width), or
+   the two camera models' raw sizes when the loop rectifies.  ME_ERR_STATE
+   unless me_vo_loop_set_tonemap is on.  The two tone maps (me_tonemap16, each
+   with its camera's state) are queued on the front-end stream first, into
+   loop-owned 8-bit buffers (three pairs, slot t mod 3, the rule of the loop's
+   other image slots); caller images are never written.  Then the remaps, the
+   CLAHE and every later stage run as in me_vo_loop_process on that 8-bit pair.
+   Nothing is read back: a keyframe keeps its one submission and round trip.
+   mem and the lifetime rule of caller device images are me_vo_loop_process's.
+   The keyframes of one loop all come through this entry or all through
+   me_vo_loop_process: mixing them is ME_ERR_STATE. */
+int me_vo_loop_process16(me_vo_loop* v, int t, const uint16_t* left, const uint16_t* right, me_mem mem);
 /* Completes the last keyframe (its pops, scale LM and BA). */
 int me_vo_loop_finish(me_vo_loop* v);
 /* Results of the completed keyframes (*n = their number; min(cap, *n) copied). */
@@ -880,6 +900,69 @@ int  me_clahe(me_ctx* ctx, me_mem mem, const uint8_t* src, int width, int height
    case on either side; ME_ERR_INVALID (negative) for a NULL ctx or a size
    below 1. */
 int  me_clahe_apply_rows(me_ctx* ctx, int width, int height);
+
+/* ---- A12g: 16-bit ingest, 16 -> 8-bit tone mapping (build-defined; no
+ * reference) ---------------------------------------------------------------
+ * A thermal core delivers 14 or 16 bits per pixel and a scene often spans a
+ * few hundred counts of them; keeping the high byte leaves a handful of
+ * levels.  me_tonemap16 maps a percentile window of the 16-bit image linearly
+ * to 0..255; the window follows the scene through a temporal filter whose
+ * state lives on the device.  The definition is this library's own, integer
+ * only: it restates no OpenCV function and parity is unpinned.  The numpy
+ * restatement is uasl_motion_estimation_amd/tonemap.py (tonemap_ref), the
+ * checker; image and state are bit-exact.
+ *
+ * Input: uint16 image, width x height, stride in elements; N = width*height.
+ * State (per camera): three int32 words lo_q8, hi_q8, frames.
+ *   1. frame window.  h = the histogram of the N pixels over 0..65535, c its
+ *      inclusive prefix sum.  k_lo = floor(lo_ppm*N / 10^6), k_hi =
+ *      floor(hi_ppm*N / 10^6) (64-bit products).  lo = the smallest v with
+ *      c[v] > k_lo; hi = the smallest v with c[v] >= N - k_hi.  lo <= hi since
+ *      lo_ppm + hi_ppm < 10^6.
+ *   2. minimum span.  s = hi - lo; if s < min_span: lo -= (min_span - s) / 2
+ *      (C division); if lo < 0: lo = 0; hi = lo + min_span; if hi > 65535:
+ *      hi = 65535, lo = 65535 - min_span.
+ *   3. temporal filter (int64 intermediates, floor division = arithmetic
+ *      shift).  frames == 0: lo_q8 = lo << 8, hi_q8 = hi << 8.  Otherwise
+ *      x_q8 += floor(((x << 8) - x_q8) * alpha_q8 / 256) for both words.
+ *      frames += 1, saturating at INT32_MAX.  alpha_q8 = 256: no memory.
+ *   4. window used.  lo_u = lo_q8 >> 8, hi_u = (hi_q8 + 255) >> 8,
+ *      span = max(1, hi_u - lo_u).
+ *   5. map.  v < lo_u: 0.  Otherwise q = (min(v, hi_u) - lo_u)*255 + span/2
+ *      and out = min(255, q / span).  Every product is below 2^24.
+ * Nothing depends on scheduling.  Elements of a row past its width (stride
+ * padding) are never read as pixels nor written.
+ *
+ * The defaults (1000, 1000, 256, 64: 0.1 % clipped at either end, at least
+ * 256 counts, a quarter of the way to the new window per frame) are a choice,
+ * not a measurement.
+ *
+ * ME_ERR_INVALID, with a message that names the argument: NULL ctx / src /
+ * dst / params; width or height < 1; src_stride or dst_stride below the
+ * width; lo_ppm or hi_ppm < 0, or lo_ppm + hi_ppm >= 10^6; min_span outside
+ * 1..65535; alpha_q8 outside 1..256; src_stride * height or dst_stride *
+ * height >= 2^30; a src that is not 2-byte aligned; a state of another ctx.
+ * state = NULL: stateless, as frames = 0 (nothing is kept).  A state is used
+ * by one call at a time, in stream order.
+ * ME_DEVICE: src / dst are device memory; the call is asynchronous on the ctx
+ * stream and nothing is read back: the window goes from the select kernels to
+ * the apply kernel through device memory.  ME_HOST: src / dst are host memory,
+ * the call is staged in a scratch slot of its own and synchronous; dst is
+ * returned row by row, so the caller's row padding keeps its bytes.  The state
+ * is device memory in both modes.  Three kernels (coarse select, fine select,
+ * apply; one launch each) are timed in the ME_KT_TONEMAP family. */
+typedef struct me_tonemap_params { int lo_ppm, hi_ppm, min_span, alpha_q8; } me_tonemap_params;
+typedef struct me_tonemap_state me_tonemap_state;
+void me_tonemap_default_params(me_tonemap_params* p);             /* 1000, 1000, 256, 64 */
+int  me_tonemap_state_create(me_ctx* ctx, me_tonemap_state** st);  /* frames = 0 */
+int  me_tonemap_state_destroy(me_tonemap_state* st);
+/* Asynchronous on the state's ctx stream: frames = 0 (the next call starts a new window). */
+int  me_tonemap_state_reset(me_tonemap_state* st);
+/* Synchronous: out = {lo_q8, hi_q8, frames}. */
+int  me_tonemap_state_read(me_tonemap_state* st, int32_t out[3]);
+int  me_tonemap16(me_ctx* ctx, me_mem mem, const uint16_t* src, int width, int height, int src_stride,
+                  uint8_t* dst, int dst_stride, const me_tonemap_params* params,
+                  me_tonemap_state* state /* NULL: stateless, as frames = 0 */);
 
 /* ---- A11: non-maximum suppression ------------------------------------
  * Replaces std::vector<pt2D> me::nonMaxSupScanline3x3(const cv::Mat& input,

@@ -35,6 +35,11 @@ loads another build of libme_hip.so (tools/build_variant.sh).
                          me_clahe (1280x720, 3840x2160; noise and a 16-level low-contrast image, 8x8 tiles), the
                          table kernel and the apply kernel apart, beside the library's streaming copy of the same
                          bytes, and the config-3 native loop with the equaliser off / on, alternating
+  tonemap [--reps --check --loop N]
+                         me_tonemap16 (640x480, 1280x720, 3840x2160; 14-bit noise and a 16-level low-entropy
+                         image), the coarse select apart from fine select + apply, beside the library's streaming
+                         copy of the same bytes, and the config-3 native loop on the 8-bit stream / on its 16-bit
+                         twin through me_vo_loop_process16, alternating
 """
 import argparse
 import ctypes
@@ -1173,6 +1178,130 @@ def cmd_clahe(a):
     print(json.dumps(out))
 
 
+def cmd_tonemap(a):
+    """The 16-bit ingest (csrc/tonemap.hip): me_tonemap16 on one state --reps
+    times after 20 warm-up calls per size (640x480, 1280x720, 3840x2160) and
+    image (14-bit noise; the low-entropy image 100*64 + v // 16, on which the
+    lanes of a wave meet on a few histogram words), default parameters,
+    HIP-event times of the ME_KT_TONEMAP family.  A call launches the coarse
+    select, the fine select and the apply kernel: one timed run takes every
+    launch, a second one every third (me_timing_sample(3): the coarse
+    selects); fine select + apply is the difference (the family's sampling
+    cannot part those two).  The yardstick is me_hbm_copy_gbs moving the same
+    algorithmic bytes: 2 B read per pixel for each select pass, 2 B read + 1 B
+    written for the apply.  With --check image and state are compared with the
+    numpy restatement at full size.  Then the config-3 native loop over --loop
+    corridor keyframes, the 8-bit stream through me_vo_loop_process against
+    its 16-bit twin 7000 + 2 v through me_vo_loop_process16, alternating, two
+    timed runs each."""
+    ctx = _setup(a.lib)
+    from uasl_motion_estimation_amd import pipeline as PL, synthetic as S, tonemap as TM
+
+    V = ctypes.c_void_p
+    out = {"lib": a.lib or "in-tree", "reps": a.reps}
+    ok = True
+    params = TM.ToneMap()
+    pc = params.to_c()
+    for (W, H) in ((640, 480), (1280, 720), (3840, 2160)):
+        npx = W * H
+        gb_1, gb_2 = ctypes.c_double(), ctypes.c_double()
+        # (the copy reads and writes its buffer once: npx bytes move 2 npx, 2.5 npx bytes move 5 npx)
+        ctx.check(ctx.lib.me_hbm_copy_gbs(ctx.h, npx, 50, ctypes.byref(gb_1)), "me_hbm_copy_gbs")
+        ctx.check(ctx.lib.me_hbm_copy_gbs(ctx.h, 5 * npx // 2, 50, ctypes.byref(gb_2)), "me_hbm_copy_gbs")
+        for name in ("noise", "low"):
+            src = (np.random.default_rng(5).integers(0, 1 << 14, (H, W), dtype=np.uint16) if name == "noise"
+                   else (100 * 64 + (_low_contrast(W, H).astype(np.uint16) - 100)).astype(np.uint16))
+            d_src, d_dst = ctx.malloc(2 * npx), ctx.malloc(npx)
+            ctx.h2d(d_src, src)
+            st = TM.ToneMapState(ctx)
+
+            def call():
+                ctx.check(ctx.lib.me_tonemap16(ctx.h, 1, V(d_src), W, H, W, V(d_dst), W, ctypes.byref(pc), st.h),
+                          "me_tonemap16")
+
+            for _ in range(20):
+                call()
+            ctx.synchronize()
+            ctx.timing(True, ["TONEMAP"])
+            res = []
+            for every in (1, 3):
+                ctx.timing_sample(every)
+                ctx.timing_reset()
+                for _ in range(a.reps):
+                    call()
+                ctx.synchronize()
+                res.append(ctx.timing_read("TONEMAP"))
+            ctx.timing_sample(1)
+            ctx.timing(False)
+            (n_all, ms_all), (n_co, ms_co) = res
+            assert n_all == 3 * a.reps and n_co == a.reps, (n_all, n_co)
+            all_us, coarse_us = 1e3 * ms_all / a.reps, 1e3 * ms_co / n_co
+            rest_us = all_us - coarse_us
+            copy_1, copy_2 = 2.0 * npx / gb_1.value * 1e-3, 5.0 * npx / gb_2.value * 1e-3  # us
+            r = {"size": f"{W}x{H}", "image": name, "calls": a.reps, "coarse_us": round(coarse_us, 2),
+                 "fine_plus_apply_us": round(rest_us, 2), "all_us": round(all_us, 2),
+                 "copy_same_bytes_coarse_us": round(copy_1, 2), "copy_same_bytes_fine_plus_apply_us": round(copy_2, 2),
+                 "coarse_fraction_of_copy": round(copy_1 / coarse_us, 3),
+                 "fine_plus_apply_fraction_of_copy": round(copy_2 / rest_us, 3)}
+            if a.check:
+                st.reset()
+                call()
+                got = np.zeros((H, W), np.uint8)
+                ctx.d2h(got, d_dst)
+                want, want_st = TM.tonemap_ref(src, params)
+                r["state_bit_exact"] = bool(st.read() == want_st)
+                r["image_bit_exact"] = bool(np.array_equal(got, want))
+                ok = ok and r["state_bit_exact"] and r["image_bit_exact"]
+            st.close()
+            for p in (d_src, d_dst):
+                ctx.free(p)
+            out[f"{r['size']}_{name}"] = r
+            print(json.dumps(r), flush=True)
+    if not ok:
+        sys.exit(1)
+    if a.loop > 0:
+        import torch
+
+        c, NK = 3, a.loop
+        arc = S.trajectory_arc(max(NK, 2))
+        truth = [np.concatenate([t, S.R_to_aa_robust(Rm)]) for (Rm, t) in arc]
+        K = S.intrinsics(1280, 720)
+        frames, wide = [], []
+        for c0 in range(0, NK, 50):
+            _, fr = S.corridor_frames_torch(S.SEED0 + c, 1280, 720, c0, min(50, NK - c0))
+            for (Lk, Rk, _, _) in fr:
+                frames.append((Lk.contiguous(), Rk.contiguous()))
+                wide.append(tuple((7000 + 2 * im.to(torch.int32)).to(torch.uint16).contiguous() for im in frames[-1]))
+            torch.cuda.synchronize()
+            print(f"rendered {len(frames)} keyframes", flush=True)
+        runs = []
+        for rep in range(-1, 2):  # (-1: a short untimed run, the first loop of a process pays the allocations)
+            for on in (False, True):
+                cfg = PL.PipelineConfig.from_config(c, tonemap=params if on else None)
+                vo = PL.NativeStereoVO(cfg, ctx, K, truth[0], truth[1] - truth[0], log_events=False, overlap=True)
+                src = wide if on else frames
+                t0 = time.perf_counter()
+                for t in range(NK if rep >= 0 else min(NK, 30)):
+                    vo.process(t, *src[t])
+                vo.finish()
+                dt = time.perf_counter() - t0
+                if rep < 0:
+                    vo.close()
+                    continue
+                st = vo._stats()
+                res = vo.results
+                vo.close()
+                names = ["klt_match", "first_match", "scale_submit", "window_submit", "ba_result", "scale_result"]
+                r = {"tonemap": on, "repeat": rep, "keyframes": NK, "keyframes_per_s": round(NK / dt, 2),
+                     "tracked_mean": round(float(np.mean([q.n_tracked for q in res[2:]])), 1),
+                     "host_s": round(st[0], 4), "blocked_s": round(st[1], 4),
+                     "wait_ms_per_keyframe": {k: round(1e3 * st[3 + i] / NK, 4) for i, k in enumerate(names)}}
+                runs.append(r)
+                print(json.dumps(r), flush=True)
+        out["loop_config3"] = runs
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--lib", default=os.environ.get("ME_LIB"))
@@ -1229,6 +1358,10 @@ def main():
     p.add_argument("--check", type=int, default=1)
     p.add_argument("--loop", type=int, default=200, help="keyframes of the config-3 native loop per run (0: skip)")
     p = sub.add_parser("clahe")
+    p.add_argument("--reps", type=int, default=200)
+    p.add_argument("--check", type=int, default=1)
+    p.add_argument("--loop", type=int, default=200, help="keyframes of the config-3 native loop per run (0: skip)")
+    p = sub.add_parser("tonemap")
     p.add_argument("--reps", type=int, default=200)
     p.add_argument("--check", type=int, default=1)
     p.add_argument("--loop", type=int, default=200, help="keyframes of the config-3 native loop per run (0: skip)")

@@ -11,10 +11,11 @@ from ._lib import Context, MEError, default_context, device_count, load_library 
 from .corners import (corner_params, corner_response, corner_response_ref, new_corners,  # noqa: F401
                       new_corners_ref)
 from .equalise import Clahe, clahe, clahe_ref  # noqa: F401
+from .tonemap import ToneMap, ToneMapState, tonemap_ref  # noqa: F401  (tonemap.tonemap: the device call)
 from .rectify import (CameraModel, RectifiedModel, StereoRectifier, rectify_map, rectify_map_ref,  # noqa: F401
                       remap, remap_ref)
 
 __all__ = ["Context", "MEError", "default_context", "device_count", "load_library", "corner_params",
            "corner_response", "corner_response_ref", "new_corners", "new_corners_ref", "Clahe", "clahe",
-           "clahe_ref", "CameraModel",
+           "clahe_ref", "ToneMap", "ToneMapState", "tonemap_ref", "CameraModel",
            "RectifiedModel", "StereoRectifier", "rectify_map", "rectify_map_ref", "remap", "remap_ref"]

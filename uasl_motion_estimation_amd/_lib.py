@@ -37,7 +37,7 @@ ERRORS = {
 
 # kernel timing families (me_hip.h ME_KT_*)
 KT = dict(MI=0, SCALE_RES=1, SCALE_NEQ=2, BA_LINEARIZE=3, BA_POINTS=4, BA_SCHUR=5, BA_SOLVE=6, BA_STEP=7,
-          KLT=8, PYR=9, NMS=10, CORNERS=11, RECTIFY=12, CLAHE=13)
+          KLT=8, PYR=9, NMS=10, CORNERS=11, RECTIFY=12, CLAHE=13, TONEMAP=14)
 
 
 class MEError(RuntimeError):
@@ -168,6 +168,11 @@ class ClaheParamsC(ctypes.Structure):
     _fields_ = [("tiles_x", c_int), ("tiles_y", c_int), ("clip_limit", c_double)]
 
 
+class ToneMapParamsC(ctypes.Structure):
+    """me_tonemap_params (include/me_hip.h)."""
+    _fields_ = [("lo_ppm", c_int), ("hi_ppm", c_int), ("min_span", c_int), ("alpha_q8", c_int)]
+
+
 ALLREDUCE_FN = ctypes.CFUNCTYPE(c_int, POINTER(c_double), c_int, c_void_p)
 
 # every symbol include/me_hip.h declares (checked by tests/test_abi.py)
@@ -188,6 +193,8 @@ EXPORTS = [
     "me_corner_default_params", "me_corner_response", "me_vo_new_corners",
     "me_rectify_map", "me_remap_tile_dims", "me_remap_q5", "me_vo_loop_set_rectify",
     "me_clahe_default_params", "me_clahe", "me_clahe_apply_rows", "me_vo_loop_set_equalise",
+    "me_tonemap_default_params", "me_tonemap_state_create", "me_tonemap_state_destroy", "me_tonemap_state_reset",
+    "me_tonemap_state_read", "me_tonemap16", "me_vo_loop_set_tonemap", "me_vo_loop_process16",
     "me_nms_scanline3x3",
     "me_vo_default_params", "me_vo_srand", "me_vo_rand", "me_vo_process",
     "me_mono_default_params", "me_mono_vo_process",
@@ -358,6 +365,15 @@ def load_library(path: str | None = None):
                              c_void_p]),
         "me_clahe_apply_rows": (c_int, [c_void_p, c_int, c_int]),
         "me_vo_loop_set_equalise": (c_int, [c_void_p, P(ClaheParamsC)]),
+        "me_tonemap_default_params": (None, [P(ToneMapParamsC)]),
+        "me_tonemap_state_create": (c_int, [c_void_p, P(c_void_p)]),
+        "me_tonemap_state_destroy": (c_int, [c_void_p]),
+        "me_tonemap_state_reset": (c_int, [c_void_p]),
+        "me_tonemap_state_read": (c_int, [c_void_p, P(ctypes.c_int32)]),
+        "me_tonemap16": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, P(ToneMapParamsC),
+                                 c_void_p]),
+        "me_vo_loop_set_tonemap": (c_int, [c_void_p, P(ToneMapParamsC)]),
+        "me_vo_loop_process16": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int]),
         "me_nms_scanline3x3": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int,
                                        P(c_int)]),
         "me_vo_default_params": (None, [P(VOParamsC)]),

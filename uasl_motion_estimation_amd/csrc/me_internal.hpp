@@ -70,6 +70,7 @@ struct me_ctx {
   long scale_counters[4] = {0, 0, 0, 0};  // last solve: residual / normal-equation evaluations, LM rejections, executed residual evaluations
   // MI term tables, one per patch pixel count N (built on first use, mi.hip)
   float* mi_table[256] = {nullptr};
+  bool tonemap_armed = false;  // the stateless block of me_tonemap16 holds zeroed tables and tickets (tonemap.hip)
 };
 
 // Multi-GPU communicator (comm.hip): RCCL, or a caller callback.
@@ -115,6 +116,8 @@ int me_check_launch(me_ctx* ctx, const char* what);
 
 // me_clahe's parameter checks against an image size (clahe.hip): NULL, or the message naming the argument.
 const char* me_clahe_check(const me_clahe_params* p, int width, int height);
+// me_tonemap16's parameter checks (tonemap.hip): NULL, or the message naming the argument.
+const char* me_tonemap_check(const me_tonemap_params* p);
 
 // roctx range (rocprofv3 --marker-trace) around an entry point's host work.
 struct me_range {
@@ -140,6 +143,6 @@ enum {
   SLOT_IMG_L = 0, SLOT_IMG_R, SLOT_XY_L, SLOT_XY_R, SLOT_MI_OUT, SLOT_RED, SLOT_GENERIC,
   SLOT_SC_TRACKS, SLOT_SC_RES, SLOT_SC_RES2, SLOT_SC_NEQ, SLOT_SC_IMGL, SLOT_SC_IMGR,
   SLOT_KLT_PYR, SLOT_KLT_PTS, SLOT_NMS, SLOT_VO, SLOT_EPI, SLOT_MONO, SLOT_CORNERS,
-  SLOT_RECTIFY, SLOT_CLAHE,
+  SLOT_RECTIFY, SLOT_CLAHE, SLOT_TONEMAP, SLOT_TONEMAP_WORK,
   SLOT_COUNT
 };

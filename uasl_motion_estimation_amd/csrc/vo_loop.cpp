@@ -246,6 +246,16 @@ struct me_vo_loop {
   bool equalise = false;
   me_clahe_params eq_params{};
   void* eq_slot[3] = {nullptr, nullptr, nullptr};
+  // ---- 16-bit ingest (me_vo_loop_set_tonemap): the parameters, a state per camera, one upload buffer for host
+  // images and three 8-bit pairs (allocated on first use; the rule of img_slot).  depth: the entry point the
+  // loop's keyframes come through (0: none yet, 8, 16)
+  bool tonemap = false;
+  me_tonemap_params tm_params{};
+  me_tonemap_state* tm_state[2] = {nullptr, nullptr};
+  void* tm_raw = nullptr;
+  void* tm_slot[3] = {nullptr, nullptr, nullptr};
+  int depth = 0;
+  bool own_device_pair = false;  // process16 only: the device pair handed to frame_images is the loop's (tm_slot)
   bool has_prev = false;
   int prev_t = -1;
   // ---- lagged state
@@ -448,6 +458,7 @@ struct me_vo_loop {
       if (b.p) me_free(tctx, b.p);
     rectify_off();
     equalise_off();
+    tonemap_off();
     for (auto& kv : dev) me_free(tctx, kv.second.p);
     for (auto& kv : pin) me_host_free(tctx, kv.second.p);
     dev.clear();
@@ -591,6 +602,53 @@ struct me_vo_loop {
     return ME_OK;
   }
 
+  void tonemap_off() {
+    for (auto& p : tm_slot) {
+      if (p) me_free(tctx, p);
+      p = nullptr;
+    }
+    if (tm_raw) me_free(tctx, tm_raw);
+    tm_raw = nullptr;
+    for (auto& st : tm_state) {
+      if (st) me_tonemap_state_destroy(st);
+      st = nullptr;
+    }
+    tonemap = false;
+  }
+  int tonemap_on(const me_tonemap_params* p) {
+    tonemap_off();
+    for (auto& st : tm_state) VL_TRY(me_tonemap_state_create(tctx, &st), "me_tonemap_state_create");
+    tm_params = *p;
+    tonemap = true;
+    return ME_OK;
+  }
+  // Keyframe t's 16-bit pair -> its 8-bit pair in tm_slot[t % 3], two me_tonemap16 queued on the front-end
+  // stream ahead of everything else; sizes are the loop's, or the camera models' when it rectifies.  The
+  // 8-bit pair then enters frame_images as device images nobody else writes.
+  int tonemap_pair(int t, const uint16_t* L, const uint16_t* R, me_mem mem, const uint8_t** oL, const uint8_t** oR) {
+    const int w[2] = {rectify ? raw_w[0] : cfg.width, rectify ? raw_w[1] : cfg.width};
+    const int h[2] = {rectify ? raw_h[0] : cfg.height, rectify ? raw_h[1] : cfg.height};
+    const size_t nl = (size_t)w[0] * h[0], nr = (size_t)w[1] * h[1];
+    if (mem != ME_DEVICE) {
+      if (tm_raw == nullptr) VL_TRY(me_malloc(tctx, &tm_raw, 2 * (nl + nr) + 16), "malloc");
+      uint16_t* dl = (uint16_t*)tm_raw;
+      uint16_t* dr = (uint16_t*)((uint8_t*)tm_raw + ((2 * nl + 15) & ~(size_t)15));
+      VL_TRY(me_memcpy_async(tctx, dl, L, 2 * nl), "image upload");
+      VL_TRY(me_memcpy_async(tctx, dr, R, 2 * nr), "image upload");
+      L = dl;
+      R = dr;
+    }
+    void*& p = tm_slot[t % 3];
+    if (p == nullptr) VL_TRY(me_malloc(tctx, &p, nl + nr + 16), "malloc");
+    uint8_t* o = (uint8_t*)p;
+    uint8_t* o2 = o + ((nl + 15) & ~(size_t)15);
+    VL_TRY(me_tonemap16(tctx, ME_DEVICE, L, w[0], h[0], w[0], o, w[0], &tm_params, tm_state[0]), "me_tonemap16");
+    VL_TRY(me_tonemap16(tctx, ME_DEVICE, R, w[1], h[1], w[1], o2, w[1], &tm_params, tm_state[1]), "me_tonemap16");
+    *oL = o;
+    *oR = o2;
+    return ME_OK;
+  }
+
   int frame_images(int t, const uint8_t* L, const uint8_t* R, me_mem mem) {
     if (imgs.count(t)) return ME_OK;
     if (rectify) return frame_images_rectified(t, L, R, mem);
@@ -611,7 +669,8 @@ struct me_vo_loop {
       im.R = (const uint8_t*)b.p + nb;
     }
     if (equalise) {
-      const int rc = equalise_pair(t, im, mem != ME_DEVICE);
+      // (in place where the pair is the loop's: an uploaded copy, or process16's tone-mapped pair)
+      const int rc = equalise_pair(t, im, mem != ME_DEVICE || own_device_pair);
       if (rc != ME_OK) return rc;
     }
     imgs[t] = im;
@@ -1547,6 +1606,23 @@ int me_vo_loop_set_equalise(me_vo_loop* v, const me_clahe_params* p) {
   return ME_OK;
 }
 
+int me_vo_loop_set_tonemap(me_vo_loop* v, const me_tonemap_params* p) {
+  if (!v) return ME_ERR_INVALID;
+  if (v->has_prev || v->failed) {
+    v->err = "me_vo_loop_set_tonemap: the tone map is set before the first me_vo_loop_process";
+    return ME_ERR_STATE;
+  }
+  v->tonemap_off();
+  if (!p) return ME_OK;
+  if (const char* why = me_tonemap_check(p)) {
+    v->err = std::string("me_vo_loop_set_tonemap: ") + why;
+    return ME_ERR_INVALID;
+  }
+  const int rc = v->tonemap_on(p);
+  if (rc != ME_OK) v->tonemap_off();
+  return rc;
+}
+
 int me_vo_loop_process(me_vo_loop* v, int t, const uint8_t* left, const uint8_t* right, me_mem mem) {
   if (!v || !left || !right) return ME_ERR_INVALID;
   if (t != (v->has_prev ? v->prev_t + 1 : 0)) {
@@ -1557,9 +1633,43 @@ int me_vo_loop_process(me_vo_loop* v, int t, const uint8_t* left, const uint8_t*
     v->err = "me_vo_loop_process: an earlier call failed (" + v->err + "); the loop state is undefined";
     return ME_ERR_STATE;
   }
+  if (v->depth == 16) {
+    v->err = "me_vo_loop_process: this loop's keyframes come through me_vo_loop_process16";
+    return ME_ERR_STATE;
+  }
+  v->depth = 8;
   me_range range_("me_vo_loop_process");
   const int rc = v->process(t, left, right, mem);
   if (rc != ME_OK) v->failed = true;  // the loop may have stopped half-way through a keyframe
+  return rc;
+}
+
+int me_vo_loop_process16(me_vo_loop* v, int t, const uint16_t* left, const uint16_t* right, me_mem mem) {
+  if (!v || !left || !right) return ME_ERR_INVALID;
+  if (!v->tonemap) {
+    v->err = "me_vo_loop_process16: 16-bit keyframes need me_vo_loop_set_tonemap";
+    return ME_ERR_STATE;
+  }
+  if (t != (v->has_prev ? v->prev_t + 1 : 0)) {
+    v->err = "me_vo_loop_process16: keyframes must come in order 0, 1, 2, ...";
+    return ME_ERR_STATE;
+  }
+  if (v->failed) {
+    v->err = "me_vo_loop_process16: an earlier call failed (" + v->err + "); the loop state is undefined";
+    return ME_ERR_STATE;
+  }
+  if (v->depth == 8) {
+    v->err = "me_vo_loop_process16: this loop's keyframes come through me_vo_loop_process";
+    return ME_ERR_STATE;
+  }
+  v->depth = 16;
+  me_range range_("me_vo_loop_process16");
+  const uint8_t *l8 = nullptr, *r8 = nullptr;
+  int rc = v->tonemap_pair(t, left, right, mem, &l8, &r8);
+  v->own_device_pair = true;
+  if (rc == ME_OK) rc = v->process(t, l8, r8, ME_DEVICE);
+  v->own_device_pair = false;
+  if (rc != ME_OK) v->failed = true;
   return rc;
 }
 

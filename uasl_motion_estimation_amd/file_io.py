@@ -351,6 +351,24 @@ def imread_gray(path: str) -> np.ndarray | None:
         return None
 
 
+def imread_gray16(path: str) -> np.ndarray | None:
+    """A grayscale PNG with all its bits, (h, w) uint16: a 16-bit file as it is
+    (imread_gray keeps its high byte only), any other file through imread_gray
+    and widened x 257 (0 -> 0, 255 -> 65535).  None when unreadable.  What
+    PipelineConfig.tonemap reduces to 8 bits (tonemap.py)."""
+    from PIL import Image
+
+    try:
+        with Image.open(path) as im:
+            im.load()
+            if im.mode in ("I;16", "I;16B", "I;16L", "I"):
+                return np.clip(np.asarray(im).astype(np.int64), 0, 65535).astype(np.uint16)
+    except (OSError, ValueError):
+        return None
+    g = imread_gray(path)
+    return None if g is None else (g.astype(np.uint16) * np.uint16(257))
+
+
 def _num(nb: int, padding: int) -> str:
     return str(int(nb)).zfill(padding) if nb >= 0 else "-" + str(-int(nb)).zfill(padding - 1)
 

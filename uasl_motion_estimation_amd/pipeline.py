@@ -129,6 +129,7 @@ class PipelineConfig:
     klt_predict: bool = False     # True: the tracker starts at each landmark's predicted pixel (predict_uv, klt_ref.py)
     rectify: "StereoRectifier | None" = None  # rectify.StereoRectifier: process() takes raw images and warps them first
     equalise: "Clahe | None" = None  # equalise.Clahe: both images of a keyframe are equalised ahead of the tracker
+    tonemap: "ToneMap | None" = None  # tonemap.ToneMap: process() takes uint16 images and reduces them to 8 bits first
 
     def __post_init__(self):
         if self.rectify is not None:
@@ -145,6 +146,11 @@ class PipelineConfig:
             if not isinstance(self.equalise, Clahe):
                 raise ValueError("equalise must be an equalise.Clahe or None")
             self.equalise.check_size(self.width, self.height, "equalise")
+        if self.tonemap is not None:
+            from .tonemap import ToneMap
+
+            if not isinstance(self.tonemap, ToneMap):
+                raise ValueError("tonemap must be a tonemap.ToneMap or None")
         if self.detector not in DETECTORS:
             raise ValueError(f"detector must be one of {DETECTORS}")
         if not self.klt_fb_max >= 0.0:  # (false for NaN)
@@ -400,6 +406,9 @@ class Backend:
     rectifies = False  # True: frame_images takes raw images and warps them itself (on the device)
     equaliser = None  # PipelineConfig.equalise of the loop's configuration (None: the images are used as they come)
     equalises = False  # True: frame_images equalises itself (on the device)
+    tonemapper = None  # PipelineConfig.tonemap of the loop's configuration (None: uint16 images are refused)
+    tonemaps = False  # True: frame_images takes uint16 images and tone-maps them itself (on the device)
+    _tm_state = None  # host backends: the two cameras' (lo_q8, hi_q8, frames)
 
     def frame_images(self, t: int, left: np.ndarray, right: np.ndarray):
         raise NotImplementedError
@@ -416,6 +425,22 @@ class Backend:
         if self.rectifies:
             return left, right
         return self.rectifier.apply_ref(left, right)
+
+    def tonemapped_pair(self, left, right):
+        """uint16 images of a keyframe -> the 8-bit pair every later step gets
+        (first of all: ahead of rectified_pair): a host backend (tonemaps =
+        False) maps here with the numpy restatement (tonemap.tonemap_ref), each
+        camera with a state of its own; on a backend that maps on the device
+        the images pass through."""
+        if self.tonemaps:
+            return left, right
+        from .tonemap import tonemap_ref
+
+        st = self._tm_state or [None, None]
+        left, st[0] = tonemap_ref(left, self.tonemapper, st[0])
+        right, st[1] = tonemap_ref(right, self.tonemapper, st[1])
+        self._tm_state = st
+        return left, right
 
     def equalised_pair(self, left, right):
         """The pair frame_images gets, after rectified_pair: a host backend
@@ -657,6 +682,32 @@ class GPUBackend(Backend):
 
     rectifies = True  # raw images are warped on the front-end context (me_remap_q5), not on the host
     equalises = True  # me_clahe on the front-end context, not on the host
+    tonemaps = True  # me_tonemap16 on the front-end context, not on the host
+    _tm_dev = None  # the two cameras' tonemap.ToneMapState on the front-end context
+
+    def _check_wide(self, shape_l, shape_r, who):
+        """Everything that can refuse a uint16 pair, before anything is allocated for it."""
+        if self.tonemapper is None:
+            raise ValueError(f"{who}: uint16 images need PipelineConfig.tonemap")
+        if len(shape_l) != 2 or len(shape_r) != 2:
+            raise ValueError(f"{who}: (h, w) uint16 images expected, got {shape_l} and {shape_r}")
+        if self.rectifier is not None:
+            self.rectifier.check_raw(shape_l, shape_r, who)
+        elif shape_l != shape_r:
+            raise ValueError(f"{who}: left is {shape_l}, right {shape_r}")
+
+    def _tonemapped(self, d_left, d_right, shape_l, shape_r):
+        """Two me_tonemap16 of dense uint16 device images queued on the
+        front-end stream, each with its camera's state, into new 8-bit buffers
+        of the backend's; returns the two."""
+        from .tonemap import ToneMapState, tonemap_device
+
+        if self._tm_dev is None:
+            self._tm_dev = [ToneMapState(self.tctx), ToneMapState(self.tctx)]
+        oL, oR = self.tctx.malloc(shape_l[0] * shape_l[1]), self.tctx.malloc(shape_r[0] * shape_r[1])
+        tonemap_device(self.tctx, self.tonemapper, self._tm_dev[0], d_left, shape_l[1], shape_l[0], oL)
+        tonemap_device(self.tctx, self.tonemapper, self._tm_dev[1], d_right, shape_r[1], shape_r[0], oR)
+        return oL, oR
 
     def _rectified(self, t, d_left, d_right, raw):
         """Handle of keyframe t's rectified pair: two remaps of the raw device
@@ -685,6 +736,24 @@ class GPUBackend(Backend):
     def frame_images(self, t, left, right):
         if t in self._imgs:
             return self._imgs[t]
+        if np.asarray(left).dtype == np.uint16:  # tone-mapped first; the 8-bit pair is the backend's own
+            L, R = np.ascontiguousarray(left), np.asarray(right)
+            if R.dtype != np.uint16:
+                raise ValueError(f"GPUBackend.frame_images: left is uint16, right {R.dtype}")
+            R = np.ascontiguousarray(R)
+            self._check_wide(L.shape, R.shape, "GPUBackend.frame_images")
+            d16 = (self.tctx.malloc(L.nbytes), self.tctx.malloc(R.nbytes))
+            self.tctx.h2d(d16[0], L)
+            self.tctx.h2d(d16[1], R)
+            dL, dR = self._tonemapped(d16[0], d16[1], L.shape, R.shape)
+            if self.rectifier is not None:
+                return self._rectified(t, dL, dR, (dL, dR) + d16)
+            self._equalise(dL, dR, dL, dR, L.shape)
+            ph = np.lib.stride_tricks.as_strided(np.zeros(1, np.uint8), shape=L.shape, strides=(0, 0))  # shape only
+            self._raw[t] = d16
+            h = (dL, dR, L.shape, ph, ph)
+            self._imgs[t] = h
+            return h
         L = np.ascontiguousarray(left, np.uint8)
         R = np.ascontiguousarray(right, np.uint8)
         # (on the front-end context: the BA context may be in use by the enqueue worker)
@@ -705,6 +774,22 @@ class GPUBackend(Backend):
         referenced until release(t))."""
         if t in self._imgs:
             return self._imgs[t]
+        if "uint16" in str(getattr(left, "dtype", "")):  # uint16 tensors: tone-mapped into buffers of the backend's
+            shape = tuple(left.shape)
+            for name, im in (("left", left), ("right", right)):
+                if "uint16" not in str(getattr(im, "dtype", "")) or not im.is_contiguous():
+                    raise ValueError(f"GPUBackend.frame_images_device: {name} must be a contiguous uint16 tensor, got "
+                                     f"{getattr(im, 'dtype', None)}")
+            self._check_wide(shape, tuple(right.shape), "GPUBackend.frame_images_device")
+            oL, oR = self._tonemapped(int(left.data_ptr()), int(right.data_ptr()), shape, tuple(right.shape))
+            if self.rectifier is not None:
+                return self._rectified(t, oL, oR, (oL, oR, left, right))
+            self._equalise(oL, oR, oL, oR, shape)
+            ph = np.lib.stride_tricks.as_strided(np.zeros(1, np.uint8), shape=shape, strides=(0, 0))  # shape only
+            self._raw[t] = (left, right)
+            h = (oL, oR, shape, ph, ph)
+            self._imgs[t] = h
+            return h
         if self.rectifier is not None:
             self.rectifier.check_raw(tuple(left.shape), tuple(right.shape), "GPUBackend.frame_images_device")
             return self._rectified(t, int(left.data_ptr()), int(right.data_ptr()), (left, right))
@@ -732,6 +817,9 @@ class GPUBackend(Backend):
                 self.tctx.free(raw)
 
     def close(self):
+        for st in self._tm_dev or ():
+            st.close()
+        self._tm_dev = None
         if self._scale_res is not None:
             self.scale_result()
         if self._scale_pool is not None:
@@ -1282,6 +1370,7 @@ class WindowedStereoVO:
         self.be.klt_predict = bool(cfg.klt_predict)
         self.be.rectifier = cfg.rectify
         self.be.equaliser = cfg.equalise
+        self.be.tonemapper = cfg.tonemap
         if hasattr(backend, "reserve"):
             backend.reserve(cfg)
         self.K = np.asarray(S.intrinsics(cfg.width, cfg.height) if K is None else K, np.float64)
@@ -1450,6 +1539,10 @@ class WindowedStereoVO:
         t_in = time.perf_counter()
         w0 = self.stage_s["wait"]
         cfg = self.cfg
+        if left is not None and np.asarray(left).dtype == np.uint16:  # 16-bit ingest: tone map -> remap -> CLAHE
+            if cfg.tonemap is None:
+                raise ValueError("WindowedStereoVO.process: uint16 images need PipelineConfig.tonemap")
+            left, right = self.be.tonemapped_pair(left, np.asarray(right))
         if self.be.rectifier is not None and left is not None:  # (None: handed to frame_images_device already)
             left, right = self.be.rectified_pair(left, right)
         if self.be.equaliser is not None and left is not None:
@@ -1816,6 +1909,9 @@ class NativeStereoVO:
             if cfg.equalise is not None:
                 pc = cfg.equalise.to_c()
                 self._check(self.lib.me_vo_loop_set_equalise(self.h, ctypes.byref(pc)), "me_vo_loop_set_equalise")
+            if cfg.tonemap is not None:
+                pc = cfg.tonemap.to_c()
+                self._check(self.lib.me_vo_loop_set_tonemap(self.h, ctypes.byref(pc)), "me_vo_loop_set_tonemap")
         except Exception:
             self.close()  # (the loop exists: destroy it, give the contexts their CUs back)
             raise
@@ -1867,32 +1963,37 @@ class NativeStereoVO:
         shapes = {"left": shape, "right": shape}
         if self.cfg.rectify is not None:  # raw images: each camera model's own size
             shapes = {"left": self.cfg.rectify.left.shape, "right": self.cfg.rectify.right.shape}
+        # 16-bit ingest: with the switch, uint16 images go to me_vo_loop_process16 (same checks otherwise)
+        wide = self.cfg.tonemap is not None and "uint16" in str(getattr(left, "dtype", ""))
+        entry, what = ((self.lib.me_vo_loop_process16, "me_vo_loop_process16") if wide
+                       else (self.lib.me_vo_loop_process, "me_vo_loop_process"))
         if hasattr(left, "data_ptr"):
             import torch
 
+            want = torch.uint16 if wide else torch.uint8
             for name, im in (("left", left), ("right", right)):
                 shape = shapes[name]
-                if not (isinstance(im, torch.Tensor) and im.dtype == torch.uint8 and tuple(im.shape) == shape
+                if not (isinstance(im, torch.Tensor) and im.dtype == want and tuple(im.shape) == shape
                         and im.is_contiguous() and im.is_cuda and im.device.index == self.ctx.device):
-                    raise ValueError(f"NativeStereoVO.process: {name} must be a contiguous uint8 tensor of shape "
+                    raise ValueError(f"NativeStereoVO.process: {name} must be a contiguous "
+                                     f"{'uint16' if wide else 'uint8'} tensor of shape "
                                      f"{shape} on cuda:{self.ctx.device}, got "
                                      f"{getattr(im, 'dtype', None)} {tuple(getattr(im, 'shape', ()))} "
                                      f"on {getattr(im, 'device', None)}")
             self._order_after_torch(left.device)
             self._keep[t] = (left, right)
             self._keep.pop(t - 2, None)
-            rc = self.lib.me_vo_loop_process(self.h, t, ctypes.c_void_p(left.data_ptr()),
-                                             ctypes.c_void_p(right.data_ptr()), ME_DEVICE)
+            rc = entry(self.h, t, ctypes.c_void_p(left.data_ptr()), ctypes.c_void_p(right.data_ptr()), ME_DEVICE)
         else:
             L, R = np.asarray(left), np.asarray(right)
             for name, im in (("left", L), ("right", R)):
                 shape = shapes[name]
-                if im.dtype != np.uint8 or im.shape != shape:
-                    raise ValueError(f"NativeStereoVO.process: {name} must be a uint8 array of shape {shape}, "
-                                     f"got {im.dtype} {im.shape}")
+                if im.dtype != (np.uint16 if wide else np.uint8) or im.shape != shape:
+                    raise ValueError(f"NativeStereoVO.process: {name} must be a {'uint16' if wide else 'uint8'} array "
+                                     f"of shape {shape}, got {im.dtype} {im.shape}")
             L, R = np.ascontiguousarray(L), np.ascontiguousarray(R)
-            rc = self.lib.me_vo_loop_process(self.h, t, L.ctypes.data, R.ctypes.data, ME_HOST)
-        self._check(rc, "me_vo_loop_process")
+            rc = entry(self.h, t, L.ctypes.data, R.ctypes.data, ME_HOST)
+        self._check(rc, what)
 
     def finish(self):
         self._check(self.lib.me_vo_loop_finish(self.h), "me_vo_loop_finish")
