@@ -382,9 +382,10 @@ int me_ba_reserve(me_ctx* ctx, int n_cams, int n_pts, int n_obs, int obs_dim, in
    landmark with ID >= new_from is new in keyframe t, moved from pose
    (rotation R, row-major) to the new pose(t) when they differ; camera
    n_cams - 1 is pose(t):
-   mode 1: c[k1] + (c[k1] - c[k0]), mode 0: c[k1] + vel, mode -1: kept.  The
-   new pose's rotation is a fixed Taylor series in theta^2 (the loop's host
-   code repeats the arithmetic bit for bit).  Asynchronous on the ctx stream. */
+   mode 1: c[k1] + (c[k1] - c[k0]), mode 0: c[k1] + vel, mode -1: kept (k1
+   and k0 are neither checked nor read).  The new pose's rotation is a fixed
+   Taylor series in theta^2 (the loop's host code repeats the arithmetic bit
+   for bit).  Asynchronous on the ctx stream. */
 typedef struct me_vo_chain_args {
   double pose[6];
   double R[9];

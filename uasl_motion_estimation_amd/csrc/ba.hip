@@ -4148,8 +4148,12 @@ __global__ __launch_bounds__(256) void vo_chain_kernel(const double* pc, const d
   if (threadIdx.x == 0) {
     double p2[6];
     for (int j = 0; j < 6; ++j) {
+      if (a.mode != 1 && a.mode != 0) {  // kept: k1 / k0 are not checked for this mode, so not read either
+        p2[j] = cams[6 * (nc - 1) + j];
+        continue;
+      }
       const double c1 = cam(a.k1, j);
-      p2[j] = a.mode == 1 ? c1 + (c1 - cam(a.k0, j)) : a.mode == 0 ? c1 + a.vel[j] : cams[6 * (nc - 1) + j];
+      p2[j] = a.mode == 1 ? c1 + (c1 - cam(a.k0, j)) : c1 + a.vel[j];
     }
     for (int j = 0; j < 6; ++j) sh[j] = p2[j];
     rot_series(p2 + 3, sh + 6);
