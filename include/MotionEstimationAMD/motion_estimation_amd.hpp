@@ -22,6 +22,7 @@
 
 #include <array>
 #include <cstdint>
+#include <cstring>
 #include <iostream>
 #include <memory>
 #include <stdexcept>
@@ -851,6 +852,70 @@ inline void calcOpticalFlowPyrLK(const amd::ImageView& prev, const amd::ImageVie
             "calcOpticalFlowPyrLK");
 }
 
+namespace amd {
+// Rigid-motion gate of tracked stereo features (A12h, me_motion_gate; no
+// reference counterpart: the reference's geometric test is the RANSAC inside
+// StereoVisualOdometry::process).  prev[i] = (u, v, x_r) of feature i in
+// keyframe t - 1, cur[i] in keyframe t; status / ok are the tracker's and the
+// matcher's bytes.  ok comes back with the byte of every usable feature that
+// does not move with the estimated camera motion cleared; err (pixels, +inf
+// where none) and info are filled.  Host vectors, staged through one device
+// block; synchronous.
+struct Point3f {
+  float x, y, z;
+};
+struct MotionGateInfo {
+  int32_t n_usable, n_valid, winner, n_inliers, abstained, reserved[3];
+  double R[9], t[3];
+};
+struct MotionGateCamera {
+  double f, cx, cy, baseline;
+  int width, height;
+  float margin;
+};
+inline void motionGate(const std::vector<Point3f>& prev, const std::vector<Point3f>& cur,
+                       const std::vector<uint8_t>& status, std::vector<uint8_t>& ok, const MotionGateCamera& cam, int t,
+                       const me_motion_gate_params& params, std::vector<float>& err, MotionGateInfo& info,
+                       Context& ctx = Context::thread_default()) {
+  static_assert(sizeof(MotionGateInfo) == 128, "me_motion_gate's info block");
+  const size_t n = prev.size();
+  if (cur.size() != n || status.size() != n || ok.size() != n)
+    throw std::invalid_argument("motionGate: one entry per feature in every array");
+  const size_t m = n ? n : 1;
+  // info | prev_uv | prev_xr | cur_uv | cur_xr | err | status | ok
+  const size_t o_puv = 128, o_pxr = o_puv + 8 * m, o_cuv = o_pxr + 4 * m, o_cxr = o_cuv + 8 * m, o_err = o_cxr + 4 * m,
+               o_st = o_err + 4 * m, o_ok = o_st + m, total = o_ok + m;
+  std::vector<uint8_t> host(total, 0);
+  for (size_t i = 0; i < n; ++i) {
+    const float puv[2] = {prev[i].x, prev[i].y}, cuv[2] = {cur[i].x, cur[i].y};
+    std::memcpy(&host[o_puv + 8 * i], puv, 8);
+    std::memcpy(&host[o_pxr + 4 * i], &prev[i].z, 4);
+    std::memcpy(&host[o_cuv + 8 * i], cuv, 8);
+    std::memcpy(&host[o_cxr + 4 * i], &cur[i].z, 4);
+    host[o_st + i] = status[i];
+    host[o_ok + i] = ok[i];
+  }
+  void* d = nullptr;
+  ctx.check(me_malloc(ctx.get(), &d, total), "motionGate");
+  uint8_t* b = static_cast<uint8_t*>(d);
+  int rc = me_memcpy_h2d(ctx.get(), d, host.data(), total);
+  if (rc == ME_OK)
+    rc = me_motion_gate(ctx.get(), (const float*)(b + o_puv), (const float*)(b + o_pxr), (const float*)(b + o_cuv),
+                        (const float*)(b + o_cxr), b + o_st, b + o_ok, (int)n, cam.f, cam.cx, cam.cy, cam.baseline,
+                        cam.width, cam.height, cam.margin, t, &params, b + o_ok, (float*)(b + o_err), b);
+  if (rc == ME_OK) rc = me_synchronize(ctx.get());
+  if (rc == ME_OK) rc = me_memcpy_d2h(ctx.get(), host.data(), d, total);
+  me_free(ctx.get(), d);
+  ctx.check(rc, "motionGate");
+  std::memcpy(&info, host.data(), sizeof(info));
+  err.resize(n);
+  if (n) {
+    std::memcpy(err.data(), &host[o_err], 4 * n);
+    std::memcpy(ok.data(), &host[o_ok], n);
+  }
+}
+}  // namespace amd
+
 // Corner response of an 8-bit image (A12b, no reference counterpart: the
 // application's feature detector): rows x cols doubles, the KLT's minimum
 // eigenvalue of the win x win window centred on each pixel, 0 where the KLT
@@ -965,6 +1030,13 @@ class WindowedStereoVO {
   // tracker starts each feature at its landmark's pixel under the predicted
   // pose; off (the default) at the feature's old position.  Before the first
   // process(); a later call throws.
+  // The rigid-motion gate of the tracked features (me_hip.h A12h): with
+  // parameters every keyframe's tracked features pass me_motion_gate behind
+  // their stereo match, nullptr switches it off (the default).  Before the
+  // first process(); bad parameters, or a later call, throw.
+  void setMotionGate(const me_motion_gate_params* params) {
+    check(me_vo_loop_set_motion_gate(v_.get(), params), "WindowedStereoVO::setMotionGate");
+  }
   void setKltPredict(bool on) {
     check(me_vo_loop_set_klt_predict(v_.get(), on ? 1 : 0), "WindowedStereoVO::setKltPredict");
   }

@@ -95,7 +95,8 @@ int me_host_free(me_ctx* ctx, void* hptr);
    stream, so time only the families a measurement needs. */
 enum { ME_KT_MI = 0, ME_KT_SCALE_RES = 1, ME_KT_SCALE_NEQ = 2, ME_KT_BA_LINEARIZE = 3, ME_KT_BA_POINTS = 4,
        ME_KT_BA_SCHUR = 5, ME_KT_BA_SOLVE = 6, ME_KT_BA_STEP = 7, ME_KT_KLT = 8, ME_KT_PYR = 9, ME_KT_NMS = 10,
-       ME_KT_CORNERS = 11, ME_KT_RECTIFY = 12, ME_KT_CLAHE = 13, ME_KT_TONEMAP = 14, ME_KT_COUNT = 16, ME_KT_ALL = 0xffff };
+       ME_KT_CORNERS = 11, ME_KT_RECTIFY = 12, ME_KT_CLAHE = 13, ME_KT_TONEMAP = 14, ME_KT_GATE = 15,
+       ME_KT_COUNT = 16, ME_KT_ALL = 0xffff };
 int me_timing_enable(me_ctx* ctx, int family_mask);
 int me_timing_read(me_ctx* ctx, int kernel, long* launches, double* total_ms);
 int me_timing_reset(me_ctx* ctx);
@@ -527,6 +528,20 @@ int me_vo_loop_process(me_vo_loop* v, int t, const uint8_t* left, const uint8_t*
    switch is left off; after the first process call: ME_ERR_STATE. */
 struct me_tonemap_params; /* defined in section A12g below */
 int me_vo_loop_set_tonemap(me_vo_loop* v, const struct me_tonemap_params* p /* NULL: off */);
+/* The rigid-motion gate inside the loop (A12h): with parameters every keyframe
+   with tracked features queues me_motion_gate right after their stereo match,
+   on the same stream, in place on the ok byte that me_vo_new_cells /
+   me_vo_new_corners and the host's `good` mask read: a rejected track leaves
+   the window and frees its cell in the same keyframe, and the keyframe keeps
+   its single submission and round trip.  The previous keyframe's x_r (4 bytes
+   per feature) is uploaded behind the tracker's input.  t is the keyframe
+   number, f / cx / cy / baseline / margin the loop's.  NULL switches the gate
+   off (the default: the loop queues what it queued without this setter).  The
+   first keyframe's matches are not gated.  Bad parameters (me_motion_gate's
+   rules) are ME_ERR_INVALID, a call after the first me_vo_loop_process
+   ME_ERR_STATE. */
+struct me_motion_gate_params; /* defined in section A12h below */
+int me_vo_loop_set_motion_gate(me_vo_loop* v, const struct me_motion_gate_params* p /* NULL: off */);
 /* Keyframe t as 16-bit images: width x height of the loop (stride = width), or
    the two camera models' raw sizes when the loop rectifies.  ME_ERR_STATE
    unless me_vo_loop_set_tonemap is on.  The two tone maps (me_tonemap16, each
@@ -964,6 +979,98 @@ int  me_tonemap_state_read(me_tonemap_state* st, int32_t out[3]);
 int  me_tonemap16(me_ctx* ctx, me_mem mem, const uint16_t* src, int width, int height, int src_stride,
                   uint8_t* dst, int dst_stride, const me_tonemap_params* params,
                   me_tonemap_state* state /* NULL: stateless, as frames = 0 */);
+
+/* ---- A12h: rigid-motion gate of the tracked features (build-defined; no
+ * reference symbol -- the reference's geometric test is the RANSAC inside
+ * StereoVisualOdometry::process, A19, which takes host arrays, draws with the
+ * host's rand() and returns synchronously).  The loop's three tests of a track
+ * (KLT status, stereo match, margin) are photometric; this one asks whether
+ * the track moved the way a rigid scene moves under one camera motion.  It
+ * estimates that motion from the tracked stereo observations and clears the
+ * ok byte of every track that does not move with it.
+ *
+ * Integer and FP64 arithmetic only; the FP64 operations are + - * / sqrt,
+ * never contracted, each expression evaluated as written below (left to
+ * right, parentheses first).  The numpy restatement is
+ * motion_gate.motion_gate_ref.
+ *
+ * Inputs per feature k = 0 .. n - 1: prev_uv (u0, v0) and prev_xr x0 of
+ * keyframe t - 1, cur_uv (u1, v1) and cur_xr x1 of keyframe t (float), the
+ * status and ok bytes.  Scalars: f, cx, cy, baseline, the image size, margin,
+ * the keyframe number t and the parameters.  fb = f * baseline,
+ * g2 = gate_max * gate_max.
+ *  1. good_k iff status_k == 1 && ok_k != 0 && u1 >= margin &&
+ *     u1 < (float)width - margin && v1 >= margin && v1 < (float)height - margin
+ *     (float comparisons: me_vo_new_cells' good).
+ *  2. usable_k iff good_k && d0 >= min_disp && d1 >= min_disp with
+ *     d0 = (double)u0 - (double)x0, d1 = (double)u1 - (double)x1.
+ *  3. triangulation of a usable feature, P from keyframe t - 1 and Q from t:
+ *     Z = fb / d, x = ((double)u - cx) * Z / f, y = ((double)v - cy) * Z / f.
+ *  4. sampling: hypothesis h = 0 .. n_hyp - 1 fills slots s = 0, 1, 2; attempt
+ *     a = 0 .. 7 of slot s draws i = (mix(key) * n) >> 32 (64-bit product) with
+ *     key = t * 0x9E3779B1 + h * 0x85EBCA77 + (8 s + a) * 0xC2B2AE3D + seed
+ *     (uint32, wrapping) and mix = lowbias32: x ^= x >> 16; x *= 0x7FEB352D;
+ *     x ^= x >> 15; x *= 0x846CA68B; x ^= x >> 16.  The slot takes the first i
+ *     that is usable and in no earlier slot; a slot without one voids h.
+ *  5. hypothesis: with (a, b) = (P_1 - P_0, P_2 - P_0): aa = a.a, bb = b.b,
+ *     c = a x b, cc = c.c; h is void unless cc > (1e-6 * aa) * bb;
+ *     e1 = a / sqrt(aa), e3 = c / sqrt(cc), e2 = e3 x e1.  The same from Q gives
+ *     f1, f2, f3 (void likewise).  x . y = (x0 y0 + x1 y1) + x2 y2 and
+ *     x x y = (x1 y2 - x2 y1, x2 y0 - x0 y2, x0 y1 - x1 y0) everywhere.
+ *     R_ij = (f1_i e1_j + f2_i e2_j) + f3_i e3_j,
+ *     t_i = Q_0i - ((R_i0 P_00 + R_i1 P_01) + R_i2 P_02).
+ *  6. residual of a usable feature under (R, t):
+ *     Y_i = ((R_i0 P_0 + R_i1 P_1) + R_i2 P_2) + t_i; uh = f * Y_0 / Y_2 + cx,
+ *     vh = f * Y_1 / Y_2 + cy, xh = uh - fb / Y_2; r = (uh - u1, vh - v1,
+ *     xh - x1) against the observations as doubles; e2 = (r0 r0 + r1 r1) + r2 r2.
+ *     inlier iff Y_2 > 0 && e2 <= g2.
+ *  7. score: the number of inliers of a hypothesis that is not void; the
+ *     winner is the first maximum.  No hypothesis: the gate abstains (9).
+ *  8. refine: `refine` times, on the inliers of the current pose:
+ *     a = f / Y_2, q = Y_2 * Y_2, g_0 = (a, 0, -(f * Y_0) / q),
+ *     g_1 = (0, a, -(f * Y_1) / q), g_2 = (a, 0, (fb - f * Y_0) / q); Jacobian
+ *     row m = (Y x g_m, g_m) (left perturbation dY = w x Y + dt).  The 27 sums
+ *     H_ij = (J_0i J_0j + J_1i J_1j) + J_2i J_2j (i <= j, row-major) and
+ *     b_i = (J_0i r_0 + J_1i r_1) + J_2i r_2 are taken in this order: a partial
+ *     per chunk of 64 consecutive feature indices, started at +0.0 and adding
+ *     the 64 slots' terms in index order (a slot without an inlier adds +0.0),
+ *     then the partials in chunk order, started at +0.0.  H d = -b by a
+ *     textbook Cholesky (column by column; L_jj = sqrt(H_jj - sum_k L_jk^2),
+ *     L_ij = (H_ij - sum_k L_ik L_jk) / L_jj, subtractions in ascending k;
+ *     forward and back substitution likewise, ascending k); a pivot that is
+ *     not > 0 ends the refinement and keeps the pose.  d = (w, dt);
+ *     c = 0.5 * w, cc = c.c, C = ((1 - cc) I + 2 c c^T + 2 [c]x) / (1 + cc)
+ *     entry by entry ((1 - cc) + 2.0 * (c_i * c_i)) / (1 + cc) on the diagonal,
+ *     (2.0 * (c_i * c_j) +- 2.0 * c_k) / (1 + cc) off it; R <- C R and
+ *     t <- C t + dt with step 6's association.  No sin or cos anywhere.
+ *  9. output: the final pose's inliers are counted.  Fewer than min_inliers
+ *     (or no hypothesis): the gate abstains, ok_out = ok_in byte for byte.
+ *     Else ok_out_k = 0 for a usable feature that is no inlier and the ok_in
+ *     byte for every other feature: a feature that is not usable is never
+ *     rejected.  ok_out may be ok_in.  err_out (n floats, may be NULL) =
+ *     (float)sqrt(e2) under the final pose for usable features with Y_2 > 0,
+ *     +inf for the others and when there is no pose.  info (128 bytes, 8-byte
+ *     aligned, may be NULL): int32 n_usable, hypotheses not void, winner (-1:
+ *     none), final inliers, abstained (0 / 1), three zero words, then R
+ *     (row-major) and t as 12 doubles (zeros without a pose).
+ * The defaults (2.0, 0.5, 256, 3, 10, 0) come from a prototype on synthetic
+ * tracks, not from real data.  Parameter errors (gate_max, min_disp not finite
+ * or <= 0, n_hyp outside 1 .. 1024, refine outside 0 .. 8, min_inliers < 3),
+ * n < 0 or n > 2^24, a null array with n > 0, f or baseline not finite or <= 0,
+ * t < 0 are ME_ERR_INVALID; n = 0 is allowed (info alone is written).  Device memory,
+ * asynchronous on the ctx stream, three launches (the triangulations; a
+ * workgroup per hypothesis; one workgroup for steps 7 - 9), timed in the
+ * ME_KT_GATE family. */
+typedef struct me_motion_gate_params {
+  double gate_max, min_disp;
+  int n_hyp, refine, min_inliers;
+  uint32_t seed;
+} me_motion_gate_params;
+void me_motion_gate_default_params(me_motion_gate_params* p);
+int  me_motion_gate(me_ctx* ctx, const float* prev_uv, const float* prev_xr, const float* cur_uv, const float* cur_xr,
+                    const uint8_t* status, const uint8_t* ok_in, int n, double f, double cx, double cy,
+                    double baseline, int width, int height, float margin, int t, const me_motion_gate_params* params,
+                    uint8_t* ok_out, float* err_out /* may be NULL */, void* info /* may be NULL */);
 
 /* ---- A11: non-maximum suppression ------------------------------------
  * Replaces std::vector<pt2D> me::nonMaxSupScanline3x3(const cv::Mat& input,

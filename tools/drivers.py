@@ -40,6 +40,10 @@ loads another build of libme_hip.so (tools/build_variant.sh).
                          image), the coarse select apart from fine select + apply, beside the library's streaming
                          copy of the same bytes, and the config-3 native loop on the 8-bit stream / on its 16-bit
                          twin through me_vo_loop_process16, alternating
+  motion_gate [--reps --repeats --check --loop N]
+                         me_motion_gate on 2000 synthetic stereo tracks at 1280x720 (a fifth on a second body, 0.25 px
+                         noise, the default parameters): HIP-event time of its three launches and the wall time per
+                         call, and the config-3 native loop with the gate off / on, alternating
 """
 import argparse
 import ctypes
@@ -1302,6 +1306,117 @@ def cmd_tonemap(a):
     print(json.dumps(out))
 
 
+def cmd_motion_gate(a):
+    """me_motion_gate alone (ME_KT_GATE events: three launches per call) and inside the config-3 native loop."""
+    import torch
+
+    from uasl_motion_estimation_amd import motion_gate as MG
+    from uasl_motion_estimation_amd import pipeline as PL
+    from uasl_motion_estimation_amd import synthetic as S
+
+    ctx = _setup(a.lib)
+    W, H, N = 1280, 720, 2000
+    f, cx, cy, b = 0.9 * W, W / 2.0, H / 2.0, S.BASELINE
+    rng = np.random.default_rng(11)
+    Z = rng.uniform(3.0, 40.0, N)
+    u, v = rng.uniform(30, W - 30, N), rng.uniform(30, H - 30, N)
+    P = np.stack([(u - cx) * Z / f, (v - cy) * Z / f, Z], 1)
+    Q = P @ S.aa_to_R(np.array([0.004, -0.02, 0.002])).T + np.array([0.03, -0.01, -0.5])
+    mov = rng.random(N) < 0.2
+    Q[mov] = P[mov] @ S.aa_to_R(np.array([0.0, 0.03, 0.0])).T + np.array([0.6, 0.0, 0.3])
+
+    def proj(X):
+        return np.stack([f * X[:, 0] / X[:, 2] + cx, f * X[:, 1] / X[:, 2] + cy, f * (X[:, 0] - b) / X[:, 2] + cx], 1)
+
+    prev = (proj(P) + rng.normal(0, 0.25, (N, 3))).astype(np.float32)
+    cur = (proj(Q) + rng.normal(0, 0.25, (N, 3))).astype(np.float32)
+    ones = np.ones(N, np.uint8)
+    p = MG.MotionGate()
+    cam = (f, cx, cy, b, W, H, PL.MARGIN)
+    out = {"inputs": f"{W}x{H}, {N} tracks, {int(mov.sum())} on a second body, 0.25 px noise, defaults", "reps": a.reps,
+           "calls": []}
+    parts = [np.ascontiguousarray(prev[:, :2]), np.ascontiguousarray(prev[:, 2]), np.ascontiguousarray(cur[:, :2]),
+             np.ascontiguousarray(cur[:, 2]), ones, ones, ones]
+    offs = [int(x) for x in np.cumsum([0] + [q.nbytes for q in parts])]
+    host = np.concatenate([q.view(np.uint8).ravel() for q in parts])
+    d = ctx.malloc(host.nbytes)
+    ctx.h2d(d, host)
+
+    def call():
+        MG.motion_gate_device(ctx, p, d + offs[0], d + offs[1], d + offs[2], d + offs[3], d + offs[4], d + offs[5], N,
+                              *cam, 7, d + offs[6])
+
+    for rep_ in range(a.repeats):
+        for _ in range(5):
+            call()
+        ctx.synchronize()
+        ctx.timing(True, ["GATE"])
+        ctx.timing_reset()
+        w0 = time.perf_counter()
+        for _ in range(a.reps):
+            call()
+        ctx.synchronize()
+        wall = (time.perf_counter() - w0) / a.reps * 1e6
+        ctx.timing(False)
+        cnt, ms = ctx.timing_read("GATE")
+        r = {"call": "me_motion_gate", "repeat": rep_, "wall_us_per_call": round(wall, 2),
+             "GATE_us_per_call": round(1000 * ms / max(cnt // 3, 1), 2), "GATE_launches_timed": cnt}
+        out["calls"].append(r)
+        print(json.dumps(r), flush=True)
+    ctx.free(d)
+    if a.check:
+        ok, err, info = MG.motion_gate_ref(prev, cur[:, :2], cur[:, 2], ones, ones, *cam, 7, p)
+        gok, gerr, ginfo = MG.motion_gate(prev, cur[:, :2], cur[:, 2], ones, ones, *cam, 7, p, ctx=ctx)
+        same = (np.array_equal(gok, ok) and np.array_equal(gerr.view(np.uint32), err.view(np.uint32))
+                and np.array_equal(ginfo["words"], MG.info_words(info)))
+        usable = np.isfinite(err) | (ok != gok)
+        out["n_usable"], out["n_inliers"] = info["n_usable"], info["n_inliers"]
+        out["movers_kept"] = int((mov & (ok != 0) & np.isfinite(err)).sum())
+        out["static_dropped"] = int((~mov & (ok == 0) & usable).sum())
+        print(f"motion_gate parity vs the restatement: {'bit-exact' if same else 'MISMATCH'} (usable "
+              f"{info['n_usable']}, inliers {info['n_inliers']}, movers kept {out['movers_kept']}, static dropped "
+              f"{out['static_dropped']})", flush=True)
+        if not same:
+            sys.exit(1)
+    if a.loop > 0:
+        c, NK = 3, a.loop
+        arc = S.trajectory_arc(max(NK, 2))
+        truth = [np.concatenate([t, S.R_to_aa_robust(R)]) for (R, t) in arc]
+        K = S.intrinsics(1280, 720)
+        frames = []
+        for c0 in range(0, NK, 50):
+            _, fr = S.corridor_frames_torch(S.SEED0 + c, 1280, 720, c0, min(50, NK - c0))
+            frames += [(Lk.contiguous(), Rk.contiguous()) for (Lk, Rk, _, _) in fr]
+            torch.cuda.synchronize()
+            print(f"rendered {len(frames)} keyframes", flush=True)
+        runs = []
+        for rep_ in range(-1, a.repeats):  # (-1: a short untimed run, the first loop of a process pays the allocations)
+            for on in (False, True):
+                cfg = PL.PipelineConfig.from_config(c, motion_gate=p if on else None)
+                vo = PL.NativeStereoVO(cfg, ctx, K, truth[0], truth[1] - truth[0], log_events=False, overlap=True)
+                t0 = time.perf_counter()
+                for t in range(NK if rep_ >= 0 else min(NK, 30)):
+                    vo.process(t, *frames[t])
+                vo.finish()
+                dt = time.perf_counter() - t0
+                if rep_ < 0:
+                    vo.close()
+                    continue
+                st = vo._stats()
+                res = vo.results
+                vo.close()
+                names = ["klt_match", "first_match", "scale_submit", "window_submit", "ba_result", "scale_result"]
+                r = {"motion_gate": on, "repeat": rep_, "keyframes": NK, "keyframes_per_s": round(NK / dt, 2),
+                     "tracked_mean": round(float(np.mean([q.n_tracked for q in res[2:]])), 1),
+                     "new_mean": round(float(np.mean([q.n_new for q in res[2:]])), 1),
+                     "host_s": round(st[0], 4), "blocked_s": round(st[1], 4),
+                     "wait_ms_per_keyframe": {k: round(1e3 * st[3 + i] / NK, 4) for i, k in enumerate(names)}}
+                runs.append(r)
+                print(json.dumps(r), flush=True)
+        out["loop_config3"] = runs
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--lib", default=os.environ.get("ME_LIB"))
@@ -1363,6 +1478,11 @@ def main():
     p.add_argument("--loop", type=int, default=200, help="keyframes of the config-3 native loop per run (0: skip)")
     p = sub.add_parser("tonemap")
     p.add_argument("--reps", type=int, default=200)
+    p.add_argument("--check", type=int, default=1)
+    p.add_argument("--loop", type=int, default=200, help="keyframes of the config-3 native loop per run (0: skip)")
+    p = sub.add_parser("motion_gate")
+    p.add_argument("--reps", type=int, default=200)
+    p.add_argument("--repeats", type=int, default=3)
     p.add_argument("--check", type=int, default=1)
     p.add_argument("--loop", type=int, default=200, help="keyframes of the config-3 native loop per run (0: skip)")
     a = ap.parse_args()

@@ -37,7 +37,7 @@ ERRORS = {
 
 # kernel timing families (me_hip.h ME_KT_*)
 KT = dict(MI=0, SCALE_RES=1, SCALE_NEQ=2, BA_LINEARIZE=3, BA_POINTS=4, BA_SCHUR=5, BA_SOLVE=6, BA_STEP=7,
-          KLT=8, PYR=9, NMS=10, CORNERS=11, RECTIFY=12, CLAHE=13, TONEMAP=14)
+          KLT=8, PYR=9, NMS=10, CORNERS=11, RECTIFY=12, CLAHE=13, TONEMAP=14, GATE=15)
 
 
 class MEError(RuntimeError):
@@ -163,6 +163,12 @@ class RectifiedModelC(ctypes.Structure):
                 ("cy", c_double)]
 
 
+class MotionGateParamsC(ctypes.Structure):
+    """me_motion_gate_params (include/me_hip.h)."""
+    _fields_ = [("gate_max", c_double), ("min_disp", c_double), ("n_hyp", c_int), ("refine", c_int),
+                ("min_inliers", c_int), ("seed", ctypes.c_uint32)]
+
+
 class ClaheParamsC(ctypes.Structure):
     """me_clahe_params (include/me_hip.h)."""
     _fields_ = [("tiles_x", c_int), ("tiles_y", c_int), ("clip_limit", c_double)]
@@ -201,6 +207,7 @@ EXPORTS = [
     "me_vo_loop_default_config", "me_vo_loop_create", "me_vo_loop_destroy", "me_vo_loop_last_error",
     "me_vo_loop_process", "me_vo_loop_finish", "me_vo_loop_results", "me_vo_loop_events", "me_vo_loop_tracks",
     "me_vo_loop_poses", "me_vo_loop_frame_obs", "me_vo_loop_frames", "me_vo_loop_stats", "me_vo_loop_set_match_lr",
+    "me_motion_gate_default_params", "me_motion_gate", "me_vo_loop_set_motion_gate",
     "me_vo_loop_set_klt_predict",
 ]
 
@@ -365,6 +372,11 @@ def load_library(path: str | None = None):
                              c_void_p]),
         "me_clahe_apply_rows": (c_int, [c_void_p, c_int, c_int]),
         "me_vo_loop_set_equalise": (c_int, [c_void_p, P(ClaheParamsC)]),
+        "me_motion_gate_default_params": (None, [P(MotionGateParamsC)]),
+        "me_motion_gate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                   c_double, c_double, c_double, c_double, c_int, c_int, c_float, c_int,
+                                   P(MotionGateParamsC), c_void_p, c_void_p, c_void_p]),
+        "me_vo_loop_set_motion_gate": (c_int, [c_void_p, P(MotionGateParamsC)]),
         "me_tonemap_default_params": (None, [P(ToneMapParamsC)]),
         "me_tonemap_state_create": (c_int, [c_void_p, P(c_void_p)]),
         "me_tonemap_state_destroy": (c_int, [c_void_p]),

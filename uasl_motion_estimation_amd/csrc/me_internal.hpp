@@ -118,6 +118,8 @@ int me_check_launch(me_ctx* ctx, const char* what);
 const char* me_clahe_check(const me_clahe_params* p, int width, int height);
 // me_tonemap16's parameter checks (tonemap.hip): NULL, or the message naming the argument.
 const char* me_tonemap_check(const me_tonemap_params* p);
+// me_motion_gate's parameter checks (motion_gate.hip): NULL, or the message naming the argument.
+const char* me_motion_gate_check(const me_motion_gate_params* p);
 
 // roctx range (rocprofv3 --marker-trace) around an entry point's host work.
 struct me_range {
@@ -143,6 +145,6 @@ enum {
   SLOT_IMG_L = 0, SLOT_IMG_R, SLOT_XY_L, SLOT_XY_R, SLOT_MI_OUT, SLOT_RED, SLOT_GENERIC,
   SLOT_SC_TRACKS, SLOT_SC_RES, SLOT_SC_RES2, SLOT_SC_NEQ, SLOT_SC_IMGL, SLOT_SC_IMGR,
   SLOT_KLT_PYR, SLOT_KLT_PTS, SLOT_NMS, SLOT_VO, SLOT_EPI, SLOT_MONO, SLOT_CORNERS,
-  SLOT_RECTIFY, SLOT_CLAHE, SLOT_TONEMAP, SLOT_TONEMAP_WORK,
+  SLOT_RECTIFY, SLOT_CLAHE, SLOT_TONEMAP, SLOT_TONEMAP_WORK, SLOT_GATE,
   SLOT_COUNT
 };

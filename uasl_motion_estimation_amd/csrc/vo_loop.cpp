@@ -207,6 +207,11 @@ struct me_vo_loop {
   me_vo_loop_config cfg{};
   double match_lr = 0.0;  // > 0: every matcher call takes its _lr form with this bound (me_vo_loop_set_match_lr)
   std::string err;
+  // the rigid-motion gate (me_vo_loop_set_motion_gate, me_hip.h A12h): queued behind the tracked features' matcher;
+  // gate_xr: byte offset of the previous keyframe's x_r in the "klt_in" device buffer of the keyframe in flight
+  bool gate = false;
+  me_motion_gate_params gate_params{};
+  size_t gate_xr = 0;
   bool klt_predict = false;  // the tracker starts at each landmark's predicted pixel (me_vo_loop_set_klt_predict)
   double f = 0, cx = 0, cy = 0;
   int nx = 1, ny = 1;
@@ -678,14 +683,18 @@ struct me_vo_loop {
   }
 
   // ---- front end
-  // guess (klt_predict): the features' predicted pixels, uploaded behind them in the same copy
-  int klt_submit(const Imgs& prev, const Imgs& cur, const std::vector<float>& pts, const std::vector<float>* guess) {
+  // guess (klt_predict): the features' predicted pixels, uploaded behind them in the same copy; prev_xr (the
+  // rigid-motion gate): the previous keyframe's x_r, behind both
+  int klt_submit(const Imgs& prev, const Imgs& cur, const std::vector<float>& pts, const std::vector<float>* guess,
+                 const std::vector<float>* prev_xr) {
     const int n = (int)pts.size() / 2;
-    const size_t in_bytes = (guess ? 16 : 8) * (size_t)n;
+    gate_xr = (guess ? 16 : 8) * (size_t)n;
+    const size_t in_bytes = gate_xr + (prev_xr ? 4 : 0) * (size_t)n;
     void *hp, *d_in, *dres;
     VL_TRY(hbuf("klt_in", in_bytes, &hp), "klt");
     std::memcpy(hp, pts.data(), 8 * (size_t)n);
     if (guess) std::memcpy((char*)hp + 8 * (size_t)n, guess->data(), 8 * (size_t)n);
+    if (prev_xr) std::memcpy((char*)hp + gate_xr, prev_xr->data(), 4 * (size_t)n);
     VL_TRY(dbuf("klt_in", in_bytes, &d_in), "klt");
     VL_TRY(dbuf("res", 14 * (size_t)n, &dres), "klt");
     VL_TRY(me_memcpy_async(tctx, d_in, hp, in_bytes), "klt H2D");
@@ -749,6 +758,14 @@ struct me_vo_loop {
     VL_TRY(epi_match(im, (const float*)dres, (const int32_t*)dl, (const uint8_t*)dl + 4 * (size_t)n,
                      r8 + 12 * (size_t)n, n, nd, 0, (float*)(r8 + 8 * (size_t)n), r8 + 13 * (size_t)n),
            "me_mi_epipolar_match");
+    if (gate) {  // in place on the ok byte the detector below and the host's good mask read
+      const uint8_t* d_in = (const uint8_t*)dev["klt_in"].p;
+      VL_TRY(me_motion_gate(tctx, (const float*)d_in, (const float*)(d_in + gate_xr), (const float*)dres,
+                            (const float*)(r8 + 8 * (size_t)n), r8 + 12 * (size_t)n, r8 + 13 * (size_t)n, n, f, cx, cy,
+                            cfg.baseline, cfg.width, cfg.height, (float)kMargin, t, &gate_params, r8 + 13 * (size_t)n,
+                            nullptr, nullptr),
+             "me_motion_gate");
+    }
     const int m = std::max(cfg.n_feats, 1);
     VL_TRY(dbuf("new", 16 + 17 * (size_t)m, &dn), "match");
     uint8_t* n8 = (uint8_t*)dn;
@@ -1260,7 +1277,7 @@ struct me_vo_loop {
     const bool klt = has_prev && !act.empty();
     if (klt) {
       const FrameObs& po = obs[prev_t];
-      std::vector<float> pts(2 * act.size());
+      std::vector<float> pts(2 * act.size()), pxr(gate ? act.size() : 0);
       const bool same = po.ids.size() == act.size() &&
                         std::equal(act.begin(), act.end(), po.ids.begin(), [&](int64_t a, int64_t pid) { return ids[a] == pid; });
       for (size_t k = 0; k < act.size(); ++k) {
@@ -1268,6 +1285,7 @@ struct me_vo_loop {
             same ? k : (size_t)(std::lower_bound(po.ids.begin(), po.ids.end(), ids[act[k]]) - po.ids.begin());
         pts[2 * k] = po.feats[4 * pos];
         pts[2 * k + 1] = po.feats[4 * pos + 1];
+        if (gate) pxr[k] = po.feats[4 * pos + 2];
       }
       std::vector<float> guess;
       if (klt_predict) {
@@ -1285,7 +1303,7 @@ struct me_vo_loop {
           guess[2 * k + 1] = Z > 0 ? (float)(f * Yc / Z + cy) : nan;
         }
       }
-      VL_TRY(klt_submit(imgs[prev_t], im, pts, klt_predict ? &guess : nullptr), "klt");
+      VL_TRY(klt_submit(imgs[prev_t], im, pts, klt_predict ? &guess : nullptr, gate ? &pxr : nullptr), "klt");
     }
     // 2. pops of frame t-1's completion
     if (has_pending) pop(pending.t + 1 - cfg.window);
@@ -1548,6 +1566,22 @@ int me_vo_loop_set_match_lr(me_vo_loop* v, double lr_max) {
     return ME_ERR_STATE;
   }
   v->match_lr = lr_max;
+  return ME_OK;
+}
+
+int me_vo_loop_set_motion_gate(me_vo_loop* v, const me_motion_gate_params* p) {
+  if (!v) return ME_ERR_INVALID;
+  if (p)
+    if (const char* why = me_motion_gate_check(p)) {
+      v->err = std::string("me_vo_loop_set_motion_gate: ") + why;
+      return ME_ERR_INVALID;
+    }
+  if (v->has_prev || v->failed) {
+    v->err = "me_vo_loop_set_motion_gate: the rigid-motion gate is set before the first me_vo_loop_process";
+    return ME_ERR_STATE;
+  }
+  v->gate = p != nullptr;
+  if (p) v->gate_params = *p;
   return ME_OK;
 }
 

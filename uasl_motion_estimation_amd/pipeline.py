@@ -130,6 +130,7 @@ class PipelineConfig:
     rectify: "StereoRectifier | None" = None  # rectify.StereoRectifier: process() takes raw images and warps them first
     equalise: "Clahe | None" = None  # equalise.Clahe: both images of a keyframe are equalised ahead of the tracker
     tonemap: "ToneMap | None" = None  # tonemap.ToneMap: process() takes uint16 images and reduces them to 8 bits first
+    motion_gate: "MotionGate | None" = None  # motion_gate.MotionGate: tracks that do not move with the camera are dropped
 
     def __post_init__(self):
         if self.rectify is not None:
@@ -151,6 +152,13 @@ class PipelineConfig:
 
             if not isinstance(self.tonemap, ToneMap):
                 raise ValueError("tonemap must be a tonemap.ToneMap or None")
+        if self.motion_gate is not None:
+            from .motion_gate import MotionGate
+
+            if not isinstance(self.motion_gate, MotionGate):
+                raise ValueError("motion_gate must be a motion_gate.MotionGate or None")
+            if not (math.isfinite(self.baseline) and self.baseline > 0.0):
+                raise ValueError("motion_gate: baseline must be finite and > 0")
         if self.detector not in DETECTORS:
             raise ValueError(f"detector must be one of {DETECTORS}")
         if not self.klt_fb_max >= 0.0:  # (false for NaN)
@@ -409,6 +417,10 @@ class Backend:
     tonemapper = None  # PipelineConfig.tonemap of the loop's configuration (None: uint16 images are refused)
     tonemaps = False  # True: frame_images takes uint16 images and tone-maps them itself (on the device)
     _tm_state = None  # host backends: the two cameras' (lo_q8, hi_q8, frames)
+    motion_gate = None  # PipelineConfig.motion_gate of the loop's configuration (None: no rigid-motion gate)
+    camera = None  # (f, cx, cy, baseline) of the loop, for the gate
+    gate_log = None  # host backends: (t, info) of every gate run (motion_gate_ref's info dict)
+    _gate_prev = None  # the previous keyframe's (u, v, x_r) of the features in flight (klt_submit's prev_xr)
 
     def frame_images(self, t: int, left: np.ndarray, right: np.ndarray):
         raise NotImplementedError
@@ -484,14 +496,37 @@ class Backend:
         raise NotImplementedError
 
     # ---- staged forms
-    def klt_submit(self, prev, cur, pts, guess=None):
+    def klt_submit(self, prev, cur, pts, guess=None, prev_xr=None):
+        """prev_xr (the rigid-motion gate): the submitted points' x_r in the
+        previous keyframe; the gate runs in klt_match when it is given."""
+        self._gate_prev = None
+        if prev_xr is not None:
+            self._gate_prev = np.concatenate([np.asarray(pts, np.float32).reshape(-1, 2),
+                                              np.asarray(prev_xr, np.float32).reshape(-1, 1)], 1)
         if guess is not None:
             return (prev, cur, np.ascontiguousarray(pts, np.float32), np.ascontiguousarray(guess, np.float32))
         return (prev, cur, np.ascontiguousarray(pts, np.float32))
 
-    def klt_match(self, h, imgs, lo, nd, dvalid):
+    def _gate_host(self, uv, st, xr, ok, imgs, t):
+        """The rigid-motion gate on the host (motion_gate.motion_gate_ref) over a
+        keyframe's tracked features: the ok mask with the rejected tracks cleared."""
+        if self.motion_gate is None or self._gate_prev is None:
+            return ok
+        from .motion_gate import motion_gate_ref
+
+        H, W = imgs[2]
+        f, cx, cy, b = self.camera
+        okb, _, info = motion_gate_ref(self._gate_prev, uv, xr, st, ok, f, cx, cy, b, W, H, MARGIN, t, self.motion_gate)
+        if self.gate_log is None:
+            self.gate_log = []
+        self.gate_log.append((t, info))
+        return okb.astype(bool)
+
+    def klt_match(self, h, imgs, lo, nd, dvalid, t=0):
         """KLT of the submitted points, then the MI search (lo, nd, dvalid per
-        point) of those that pass the KLT gate: (uv, status, xr, ok)."""
+        point) of those that pass the KLT gate: (uv, status, xr, ok).  With the
+        rigid-motion gate on (klt_submit got prev_xr), ok is the gate's, for
+        keyframe number t."""
         prev, cur, pts = h[:3]
         if len(h) > 3:  # guided: the numpy restatement of the whole tracker on the host images
             from . import klt_ref
@@ -509,7 +544,7 @@ class Backend:
         ok = np.zeros(len(uv), bool)
         xk, okk = self._match(imgs, uv[keep], lo[keep], nd, dvalid[keep], False)
         xr[keep], ok[keep] = xk, okk
-        return uv, st, xr, ok
+        return uv, st, xr, self._gate_host(uv, st, xr, ok, imgs, t)
 
     def _match(self, imgs, uv, lo, nd, dvalid, unique):
         if self.match_lr_max > 0.0:
@@ -523,7 +558,10 @@ class Backend:
         """klt_match, then the new features of the cells the good tracked
         features leave empty (new_cells) matched with the uniqueness test:
         (uv, status, xr, ok, new_uv, new_xr, new_ok)."""
-        uv, st, xr, ok = self.klt_match(h, imgs, lo, nd, dvalid)
+        if self.motion_gate is not None:
+            uv, st, xr, ok = self.klt_match(h, imgs, lo, nd, dvalid, t=t)
+        else:
+            uv, st, xr, ok = self.klt_match(h, imgs, lo, nd, dvalid)
         H, W = imgs[2]
         good = (st == 1) & in_margin(uv, W, H) & ok
         nuv = self.new_features(t, imgs, uv[good], grid, d_min)
@@ -901,22 +939,28 @@ class GPUBackend(Backend):
 
     # ---- staged calls
     # device result block of a KLT + match: uv (8n) | xr (4n) | status (n) | ok (n)
-    def klt_submit(self, prev, cur, pts, guess=None):
+    def klt_submit(self, prev, cur, pts, guess=None, prev_xr=None):
         import ctypes
 
         from ._lib import ME_DEVICE
         from .klt import klt_params
 
         n = len(pts)
+        self._gate_prev = None
         if n == 0:
             return (0, prev, cur)
         H, W = prev[2]
         c = self.tctx
         nb = 8 * n if guess is None else 16 * n  # the guess rides behind the features in the same copy
+        if prev_xr is not None:  # and the previous x_r (the rigid-motion gate) behind both
+            self._gate_prev = nb  # (its byte offset in the "klt_in" device buffer)
+            nb += 4 * n
         hp = self._hbuf("klt_in", nb)
         self._view(hp, np.float32, 2 * n)[:] = np.asarray(pts, np.float32).ravel()
         if guess is not None:
             self._view(hp, np.float32, 2 * n, 8 * n)[:] = np.asarray(guess, np.float32).ravel()
+        if prev_xr is not None:
+            self._view(hp, np.float32, n, self._gate_prev)[:] = np.asarray(prev_xr, np.float32).ravel()
         d_in = self._dbuf("klt_in", nb)
         dres = self._dbuf("res", 14 * n)
         c.copy_async(d_in, hp, nb)
@@ -962,7 +1006,20 @@ class GPUBackend(Backend):
                                            PATCH, self.d_max, 1 if unique else 0, 1.2, float(MARGIN), V(d_xr),
                                            V(d_ok)), "me_mi_epipolar_match")
 
-    def klt_match(self, h, imgs, lo, nd, dvalid):
+    def _gate(self, c, imgs, dres, n, t):
+        """me_motion_gate queued on context c behind the tracked features'
+        matcher, in place on the ok bytes of the result block dres."""
+        if self.motion_gate is None or self._gate_prev is None:
+            return
+        from .motion_gate import motion_gate_device
+
+        H, W = imgs[2]
+        f, cx, cy, b = self.camera
+        d_in = self._dbuf("klt_in", self._gate_prev + 4 * n)
+        motion_gate_device(c, self.motion_gate, d_in, d_in + self._gate_prev, dres, dres + 8 * n, dres + 12 * n,
+                           dres + 13 * n, n, f, cx, cy, b, W, H, MARGIN, t, dres + 13 * n)
+
+    def klt_match(self, h, imgs, lo, nd, dvalid, t=0):
         n = h[0]
         if n == 0:
             z = np.zeros(0, np.float32)
@@ -977,6 +1034,7 @@ class GPUBackend(Backend):
         c.copy_async(dl, hp, 5 * n)
         dres = self._dbuf("res", 14 * n)
         self._epipolar(imgs, dres, dl, dl + 4 * n, dres + 12 * n, n, nd, False, dres + 8 * n, dres + 13 * n)
+        self._gate(c, imgs, dres, n, t)
         ho = self._hbuf("out", 14 * n)
         c.copy_async(ho, dres, 14 * n)
         c.synchronize()
@@ -1008,6 +1066,7 @@ class GPUBackend(Backend):
         c.copy_async(dl, hp, 5 * n)
         dres = self._dbuf("res", 14 * n)
         self._epipolar(imgs, dres, dl, dl + 4 * n, dres + 12 * n, n, nd, False, dres + 8 * n, dres + 13 * n)
+        self._gate(c, imgs, dres, n, t)
         # new-feature block: count (16 B) | uv (8 nf) | xr (4 nf) | lo (4 nf) | ok (nf)
         m = max(nf, 1)
         dn = self._dbuf("new", 16 + 17 * m)
@@ -1371,10 +1430,12 @@ class WindowedStereoVO:
         self.be.rectifier = cfg.rectify
         self.be.equaliser = cfg.equalise
         self.be.tonemapper = cfg.tonemap
+        self.be.motion_gate = cfg.motion_gate
         if hasattr(backend, "reserve"):
             backend.reserve(cfg)
         self.K = np.asarray(S.intrinsics(cfg.width, cfg.height) if K is None else K, np.float64)
         self.f, self.cx, self.cy = self.K[0, 0], self.K[0, 2], self.K[1, 2]
+        self.be.camera = (float(self.f), float(self.cx), float(self.cy), float(cfg.baseline))
         check_rectifier_K(cfg, self.K)
         # grid of feature cells over the margin-free interior
         aw, ah = cfg.width - 2 * MARGIN, cfg.height - 2 * MARGIN
@@ -1556,13 +1617,15 @@ class WindowedStereoVO:
             aid = self.ids[act]
             # (the active tracks are exactly the features of keyframe t-1, in ID order, as a rule)
             pos = np.arange(len(pid)) if len(aid) == len(pid) and np.array_equal(aid, pid) else np.searchsorted(pid, aid)
+            # (the rigid-motion gate: the tracks' previous x_r rides up with the tracker's input)
+            gkw = {} if cfg.motion_gate is None else {"prev_xr": np.ascontiguousarray(puv[pos, 2])}
             if cfg.klt_predict:
                 # pose(t) ahead of step 3 (the pops in between change none of its inputs): each landmark's
                 # predicted pixel is where its search starts
                 guess = predict_uv(self.X[act], self._predict_pose(t), self.f, self.cx, self.cy)
-                kh = self.be.klt_submit(self.prev_imgs, imgs, np.ascontiguousarray(puv[pos, :2]), guess=guess)
+                kh = self.be.klt_submit(self.prev_imgs, imgs, np.ascontiguousarray(puv[pos, :2]), guess=guess, **gkw)
             else:
-                kh = self.be.klt_submit(self.prev_imgs, imgs, np.ascontiguousarray(puv[pos, :2]))
+                kh = self.be.klt_submit(self.prev_imgs, imgs, np.ascontiguousarray(puv[pos, :2]), **gkw)
         # 2. pops of frame t-1's completion (active tracks keep their order)
         if self._pending is not None:
             self._pop(self._pending[0] + 1 - cfg.window)
@@ -1900,6 +1963,9 @@ class NativeStereoVO:
         # (a setter, not a configuration field: me_vo_loop_config keeps its layout)
         try:
             self._check(self.lib.me_vo_loop_set_match_lr(self.h, float(cfg.match_lr_max)), "me_vo_loop_set_match_lr")
+            if cfg.motion_gate is not None:
+                gp = cfg.motion_gate.to_c()
+                self._check(self.lib.me_vo_loop_set_motion_gate(self.h, ctypes.byref(gp)), "me_vo_loop_set_motion_gate")
             if cfg.klt_predict:
                 self._check(self.lib.me_vo_loop_set_klt_predict(self.h, 1), "me_vo_loop_set_klt_predict")
             if cfg.rectify is not None:  # the loop builds the two maps itself, on its front context
