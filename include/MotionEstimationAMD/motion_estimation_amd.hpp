@@ -1111,6 +1111,34 @@ class WindowedStereoVO {
     if (!left || !right) throw std::invalid_argument("WindowedStereoVO::processDevice: null image");
     check(me_vo_loop_process(v_.get(), t, left, right, ME_DEVICE), "WindowedStereoVO::processDevice");
   }
+  // Keyframe selection inside the loop (me_hip.h A12i, me_vo_loop_set_keyframe_select):
+  // with parameters the loop takes camera frames through push() and picks its
+  // keyframes itself; nullptr switches it off (the default).  Before the first
+  // frame; bad parameters, a loop with the tone map on, or a later call, throw.
+  void setKeyframeSelect(const me_kf_params* params) {
+    check(me_vo_loop_set_keyframe_select(v_.get(), params), "WindowedStereoVO::setKeyframeSelect");
+  }
+  // one camera frame (host images as in process(), copied in): the keyframe
+  // index it became, or -1 (me_vo_loop_push)
+  int push(const amd::ImageView& left, const amd::ImageView& right) {
+    if (left.empty() || right.empty() || left.step != left.cols || right.step != right.cols)
+      throw std::invalid_argument("WindowedStereoVO::push: dense 8-bit images expected");
+    if (raw_[0]) {
+      if (left.cols != raw_[0] || left.rows != raw_[1] || right.cols != raw_[2] || right.rows != raw_[3])
+        throw std::invalid_argument("WindowedStereoVO::push: raw images of the camera models' sizes expected");
+    } else if (left.rows != height_ || left.cols != width_ || right.rows != height_ || right.cols != width_)
+      throw std::invalid_argument("WindowedStereoVO::push: images of the configured width x height expected");
+    int t = -1;
+    check(me_vo_loop_push(v_.get(), left.data, right.data, ME_HOST, &t), "WindowedStereoVO::push");
+    return t;
+  }
+  // one camera frame from device memory (processDevice()'s rules; read during the call's stream work only)
+  int pushDevice(const uint8_t* left, const uint8_t* right) {
+    if (!left || !right) throw std::invalid_argument("WindowedStereoVO::pushDevice: null image");
+    int t = -1;
+    check(me_vo_loop_push(v_.get(), left, right, ME_DEVICE, &t), "WindowedStereoVO::pushDevice");
+    return t;
+  }
   void finish() { check(me_vo_loop_finish(v_.get()), "WindowedStereoVO::finish"); }
   std::vector<me_vo_frame_result> results() const {
     int n = 0;

@@ -96,7 +96,7 @@ int me_host_free(me_ctx* ctx, void* hptr);
 enum { ME_KT_MI = 0, ME_KT_SCALE_RES = 1, ME_KT_SCALE_NEQ = 2, ME_KT_BA_LINEARIZE = 3, ME_KT_BA_POINTS = 4,
        ME_KT_BA_SCHUR = 5, ME_KT_BA_SOLVE = 6, ME_KT_BA_STEP = 7, ME_KT_KLT = 8, ME_KT_PYR = 9, ME_KT_NMS = 10,
        ME_KT_CORNERS = 11, ME_KT_RECTIFY = 12, ME_KT_CLAHE = 13, ME_KT_TONEMAP = 14, ME_KT_GATE = 15,
-       ME_KT_COUNT = 16, ME_KT_ALL = 0xffff };
+       ME_KT_KEYFRAME = 16, ME_KT_COUNT = 17, ME_KT_ALL = 0x1ffff };
 int me_timing_enable(me_ctx* ctx, int family_mask);
 int me_timing_read(me_ctx* ctx, int kernel, long* launches, double* total_ms);
 int me_timing_reset(me_ctx* ctx);
@@ -554,6 +554,39 @@ int me_vo_loop_set_motion_gate(me_vo_loop* v, const struct me_motion_gate_params
    The keyframes of one loop all come through this entry or all through
    me_vo_loop_process: mixing them is ME_ERR_STATE. */
 int me_vo_loop_process16(me_vo_loop* v, int t, const uint16_t* left, const uint16_t* right, me_mem mem);
+/* Keyframe selection inside the loop (A12i): with parameters the loop takes
+   camera frames through me_vo_loop_push and chooses its keyframes itself.
+   NULL switches it off (the default: me_vo_loop_push is ME_ERR_STATE and the
+   loop makes exactly the calls it makes without this setter).  Bad parameters
+   (me_kf_update's rules) and a loop whose tone map is on (its temporal state
+   per pushed frame is not defined) are ME_ERR_INVALID; after the first frame:
+   ME_ERR_STATE. */
+struct me_kf_params; /* defined in section A12i below */
+int me_vo_loop_set_keyframe_select(me_vo_loop* v, const struct me_kf_params* p /* NULL: off */);
+/* One camera frame (8-bit images as me_vo_loop_process takes them; ME_DEVICE
+   images are read during this call only: the loop keeps copies).
+   *keyframe_t = the keyframe index the frame became, or -1.
+    - The first frame is keyframe 0; keyframe indices are consecutive.
+    - After keyframe t the state of A12i is seeded from its active tracks, in
+      the order the next tracker call uploads them: ref_uv = cur_uv = their
+      left positions, alive = 1, gap = 0.
+    - Every later frame runs the front-end chain once (remap, CLAHE where
+      set), then the loop's tracker (me_klt_track, or me_klt_track_fb when
+      klt_fb_max > 0; not guided) from the previous pushed frame to this one
+      at cur_uv over all n features, then me_kf_update on the same stream;
+      the 32-byte info block is the frame's one read-back.
+    - flags == 0: the frame's images become the previous pushed frame and
+      nothing else in the loop moves.
+    - flags != 0: the keyframe body of me_vo_loop_process runs on the images
+      already prepared.  With gap >= 2 its tracker call is the guided form
+      (me_klt_track_guided / _guided_fb) from keyframe t - 1's image and
+      positions, the guess being cur_uv of the alive features and ref_uv of
+      the others; that guess takes the place of me_vo_loop_set_klt_predict's.
+      With gap == 1 (no frame in between) the body runs exactly as
+      me_vo_loop_process runs it.
+   A loop takes its frames through this entry or through me_vo_loop_process,
+   not both: ME_ERR_STATE. */
+int me_vo_loop_push(me_vo_loop* v, const uint8_t* left, const uint8_t* right, me_mem mem, int* keyframe_t);
 /* Completes the last keyframe (its pops, scale LM and BA). */
 int me_vo_loop_finish(me_vo_loop* v);
 /* Results of the completed keyframes (*n = their number; min(cap, *n) copied). */
@@ -1071,6 +1104,56 @@ int  me_motion_gate(me_ctx* ctx, const float* prev_uv, const float* prev_xr, con
                     const uint8_t* status, const uint8_t* ok_in, int n, double f, double cx, double cy,
                     double baseline, int width, int height, float margin, int t, const me_motion_gate_params* params,
                     uint8_t* ok_out, float* err_out /* may be NULL */, void* info /* may be NULL */);
+
+/* ---- A12i: keyframe selection between the loop's keyframes (build-defined;
+ * no reference symbol -- the reference's application, which would choose its
+ * keyframes, is absent).  The caller owns the state of the n features seeded
+ * at the last keyframe, all in device memory: ref_uv (n x 2 float, the
+ * keyframe's positions, read only), cur_uv (n x 2 float, the carried
+ * positions) and alive (n bytes), the last two updated in place.  One call per
+ * frame pushed since that keyframe folds one tracker result into it -- new_uv
+ * (n x 2 float) and status (n bytes) of a tracker call from the previous
+ * pushed frame to this one started at cur_uv -- and takes the keyframe
+ * decision.  gap is the number of frames pushed since the keyframe, this one
+ * included.
+ *
+ * Exact integers and FP64; every FP64 operation is rounded once in the order
+ * written and never contracted.  The numpy restatement is
+ * keyframe.kf_update_ref.  For each feature k, with (u, v) = new_uv_k:
+ *  1. a_k iff alive_k != 0 && status_k == 1 && isfinite(u) && isfinite(v) &&
+ *     u >= margin && u < (float)width - margin && v >= margin &&
+ *     v < (float)height - margin (float comparisons: the rule of the matcher's
+ *     status gate and of me_vo_new_cells' good).
+ *  2. if a_k: cur_uv_k = new_uv_k; otherwise cur_uv_k keeps its bits.
+ *     alive_k = a_k (0 or 1).
+ *  3. if a_k: dx = (double)cur_u - (double)ref_u, dy likewise with v,
+ *     d2_k = (dx * dx) + (dy * dy).
+ * Over all features: m = the number of a_k; med2 = the element of rank
+ * (m - 1) >> 1 of the alive d2_k in ascending order (the lower median), 0.0
+ * when m == 0.  flags: bit 0 ("few") iff 100 * (int64)m <
+ * (int64)min_tracked_pct * n, or n == 0; bit 1 ("parallax") iff thr2 > 0 &&
+ * med2 >= thr2, with thr2 = min_parallax * min_parallax formed once in FP64 on
+ * the host (min_parallax = 0 switches the rule off, as 0 does the loop's other bounds);
+ * bit 2 ("gap") iff gap >= max_gap.  The frame is a keyframe iff flags != 0.
+ * info (32 bytes, 8-byte aligned, device memory): int32 n, m, rank
+ * ((m - 1) >> 1: -1 when m == 0), flags; double med2; 8 zero bytes.
+ * ref_uv is expected finite (a d2 that is NaN has no defined place in the
+ * order).  Parameter errors (min_parallax not finite or < 0, min_tracked_pct
+ * outside 0 .. 100, max_gap < 1), gap < 1, n < 0, a null array with n > 0 and
+ * a null info are ME_ERR_INVALID; n = 0 is allowed.  The defaults are 12.0,
+ * 60, 10.  Asynchronous on the ctx stream, one launch of one workgroup for
+ * any n (the threads stride): the median is a radix select over the 64-bit
+ * patterns of the d2 (monotone as unsigned integers), eight passes of 256-bin
+ * LDS histograms; timed in the ME_KT_KEYFRAME family. */
+typedef struct me_kf_params {
+  double min_parallax;  /* pixels: a keyframe once the median displacement from the last keyframe reaches it */
+  int min_tracked_pct;  /* a keyframe once fewer than this share (percent) of the seeded features is alive */
+  int max_gap;          /* a keyframe at the latest this many frames after the last one */
+} me_kf_params;
+void me_kf_default_params(me_kf_params* p);
+int  me_kf_update(me_ctx* ctx, const float* ref_uv, float* cur_uv, uint8_t* alive, const float* new_uv,
+                  const uint8_t* status, int n, int width, int height, float margin, int gap,
+                  const me_kf_params* params, void* info);
 
 /* ---- A11: non-maximum suppression ------------------------------------
  * Replaces std::vector<pt2D> me::nonMaxSupScanline3x3(const cv::Mat& input,

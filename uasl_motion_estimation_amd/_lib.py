@@ -38,6 +38,8 @@ ERRORS = {
 # kernel timing families (me_hip.h ME_KT_*)
 KT = dict(MI=0, SCALE_RES=1, SCALE_NEQ=2, BA_LINEARIZE=3, BA_POINTS=4, BA_SCHUR=5, BA_SOLVE=6, BA_STEP=7,
           KLT=8, PYR=9, NMS=10, CORNERS=11, RECTIFY=12, CLAHE=13, TONEMAP=14, GATE=15)
+# families from 16 on (tests/test_rectify.py pins KT's values below 16): timing() / timing_read() take these names too
+KT_MORE = dict(KEYFRAME=16)
 
 
 class MEError(RuntimeError):
@@ -169,6 +171,11 @@ class MotionGateParamsC(ctypes.Structure):
                 ("min_inliers", c_int), ("seed", ctypes.c_uint32)]
 
 
+class KfParamsC(ctypes.Structure):
+    """me_kf_params (include/me_hip.h)."""
+    _fields_ = [("min_parallax", c_double), ("min_tracked_pct", c_int), ("max_gap", c_int)]
+
+
 class ClaheParamsC(ctypes.Structure):
     """me_clahe_params (include/me_hip.h)."""
     _fields_ = [("tiles_x", c_int), ("tiles_y", c_int), ("clip_limit", c_double)]
@@ -209,6 +216,7 @@ EXPORTS = [
     "me_vo_loop_poses", "me_vo_loop_frame_obs", "me_vo_loop_frames", "me_vo_loop_stats", "me_vo_loop_set_match_lr",
     "me_motion_gate_default_params", "me_motion_gate", "me_vo_loop_set_motion_gate",
     "me_vo_loop_set_klt_predict",
+    "me_kf_default_params", "me_kf_update", "me_vo_loop_set_keyframe_select", "me_vo_loop_push",
 ]
 
 class MonoParamsC(ctypes.Structure):
@@ -377,6 +385,11 @@ def load_library(path: str | None = None):
                                    c_double, c_double, c_double, c_double, c_int, c_int, c_float, c_int,
                                    P(MotionGateParamsC), c_void_p, c_void_p, c_void_p]),
         "me_vo_loop_set_motion_gate": (c_int, [c_void_p, P(MotionGateParamsC)]),
+        "me_kf_default_params": (None, [P(KfParamsC)]),
+        "me_kf_update": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                 c_float, c_int, P(KfParamsC), c_void_p]),
+        "me_vo_loop_set_keyframe_select": (c_int, [c_void_p, P(KfParamsC)]),
+        "me_vo_loop_push": (c_int, [c_void_p, c_void_p, c_void_p, c_int, P(c_int)]),
         "me_tonemap_default_params": (None, [P(ToneMapParamsC)]),
         "me_tonemap_state_create": (c_int, [c_void_p, P(c_void_p)]),
         "me_tonemap_state_destroy": (c_int, [c_void_p]),
@@ -531,7 +544,7 @@ class Context:
         """Enable HIP-event timing of every kernel family, or only of `families` (names of KT)."""
         mask = 0
         if on:
-            mask = 0xFFFF if families is None else sum(1 << KT[f] for f in families)
+            mask = 0x1FFFF if families is None else sum(1 << {**KT, **KT_MORE}[f] for f in families)
         self.check(self.lib.me_timing_enable(self.h, mask))
 
     def timing_sample(self, every: int):
@@ -544,7 +557,7 @@ class Context:
     def timing_read(self, family: str):
         n = c_long()
         ms = c_double()
-        self.check(self.lib.me_timing_read(self.h, KT[family], ctypes.byref(n), ctypes.byref(ms)))
+        self.check(self.lib.me_timing_read(self.h, {**KT, **KT_MORE}[family], ctypes.byref(n), ctypes.byref(ms)))
         return n.value, ms.value
 
 

@@ -120,6 +120,8 @@ const char* me_clahe_check(const me_clahe_params* p, int width, int height);
 const char* me_tonemap_check(const me_tonemap_params* p);
 // me_motion_gate's parameter checks (motion_gate.hip): NULL, or the message naming the argument.
 const char* me_motion_gate_check(const me_motion_gate_params* p);
+// me_kf_update's parameter checks (keyframe.hip): NULL, or the message naming the argument.
+const char* me_kf_check(const me_kf_params* p);
 
 // roctx range (rocprofv3 --marker-trace) around an entry point's host work.
 struct me_range {

@@ -213,6 +213,18 @@ struct me_vo_loop {
   me_motion_gate_params gate_params{};
   size_t gate_xr = 0;
   bool klt_predict = false;  // the tracker starts at each landmark's predicted pixel (me_vo_loop_set_klt_predict)
+  // ---- keyframe selection (me_vo_loop_set_keyframe_select / me_vo_loop_push, me_hip.h A12i).  Device block
+  // "kf" of the kf_n features seeded at the last keyframe: ref_uv (8n) | cur_uv (8n) | new_uv (8n) | alive (n) |
+  // status (n), the info block at the next 16-byte boundary.  Pushed frames are prepared into four loop-owned
+  // pairs: a new frame takes a slot that neither the previous pushed frame nor the last two keyframes hold.
+  bool kf_on = false;
+  me_kf_params kf_params{};
+  int kf_n = 0, kf_gap = 0;  // seeded features; frames pushed since the last keyframe
+  long n_pushed = 0;
+  std::vector<float> kf_ref;  // the seeded features' positions in the last keyframe
+  void* push_slot[4] = {nullptr, nullptr, nullptr, nullptr};
+  int push_prev = -1, push_kf[2] = {-1, -1};  // slots of the previous pushed frame (-1: a keyframe), the last two keyframes
+  const std::vector<float>* kf_guess = nullptr;  // set around process(): the tracker's guess, ahead of klt_predict's
   double f = 0, cx = 0, cy = 0;
   int nx = 1, ny = 1;
   double cw = 1, ch = 1;
@@ -237,6 +249,7 @@ struct me_vo_loop {
   };
   std::map<int, Imgs> imgs;
   Buf img_slot[3];
+  Imgs push_imgs;  // me_vo_loop_push: the previous pushed frame's prepared pair (while push_prev >= 0)
   // ---- rectification (me_vo_loop_set_rectify): the two maps, the raw sizes, one upload buffer for host
   // images and three rectified pairs (a keyframe's pair is read during its call and the next one, by the
   // scale LM of the call after as well: the rule of img_slot)
@@ -461,6 +474,10 @@ struct me_vo_loop {
       if (w) me_free(ctx, w);
     for (auto& b : img_slot)
       if (b.p) me_free(tctx, b.p);
+    for (auto& p : push_slot) {
+      if (p) me_free(tctx, p);
+      p = nullptr;
+    }
     rectify_off();
     equalise_off();
     tonemap_off();
@@ -1288,7 +1305,12 @@ struct me_vo_loop {
         if (gate) pxr[k] = po.feats[4 * pos + 2];
       }
       std::vector<float> guess;
-      if (klt_predict) {
+      if (kf_guess) {  // (me_vo_loop_push: the carried positions, ahead of klt_predict's projections)
+        if (kf_guess->size() != 2 * act.size()) {
+          err = "me_vo_loop_push: the carried state does not match the active tracks";
+          return ME_ERR_STATE;
+        }
+      } else if (klt_predict) {
         // pose(t) ahead of step 3 (the pops in between change none of its inputs); pipeline.predict_uv
         const Pose gp = predict_pose(t);
         const Mat3 R = aa_to_R(&gp[3]);
@@ -1303,7 +1325,9 @@ struct me_vo_loop {
           guess[2 * k + 1] = Z > 0 ? (float)(f * Yc / Z + cy) : nan;
         }
       }
-      VL_TRY(klt_submit(imgs[prev_t], im, pts, klt_predict ? &guess : nullptr, gate ? &pxr : nullptr), "klt");
+      VL_TRY(klt_submit(imgs[prev_t], im, pts, kf_guess ? kf_guess : (klt_predict ? &guess : nullptr),
+                        gate ? &pxr : nullptr),
+             "klt");
     }
     // 2. pops of frame t-1's completion
     if (has_pending) pop(pending.t + 1 - cfg.window);
@@ -1470,6 +1494,155 @@ struct me_vo_loop {
     // 9. frame t-1's FrameResult (its scale LM result), while BA(t) runs
     VL_TRY(complete_result(done, d_t, d_tr, d_new, d_act, nwp, nwo, bit, bcost), "result");
     host_s += (now_s() - t_in) - (wait_s - w0);
+    return ME_OK;
+  }
+  // ------------------------------------------------------------ me_vo_loop_push (pipeline.WindowedStereoVO.push)
+  size_t kf_info_offset() const { return 16 * ((26 * (size_t)kf_n + 15) / 16); }
+  // The front-end chain of one pushed frame, once, into push_slot[slot]: upload or copy, remap, CLAHE
+  int prepare_pushed(int slot, const uint8_t* L, const uint8_t* R, me_mem mem, Imgs& im) {
+    const size_t npx = (size_t)cfg.width * cfg.height;
+    void*& p = push_slot[slot];
+    if (p == nullptr) VL_TRY(me_malloc(tctx, &p, 2 * npx), "malloc");
+    uint8_t* o = (uint8_t*)p;
+    im.L = o;
+    im.R = o + npx;
+    if (rectify) {
+      const size_t nl = (size_t)raw_w[0] * raw_h[0], nr = (size_t)raw_w[1] * raw_h[1];
+      if (mem != ME_DEVICE) {
+        VL_TRY(me_memcpy_async(tctx, rect_raw, L, nl), "image upload");
+        VL_TRY(me_memcpy_async(tctx, (uint8_t*)rect_raw + nl, R, nr), "image upload");
+        L = (const uint8_t*)rect_raw;
+        R = L + nl;
+      }
+      VL_TRY(me_remap_q5(tctx, ME_DEVICE, L, raw_w[0], raw_h[0], raw_w[0], (const int32_t*)rect_map[0], cfg.width,
+                         cfg.height, rect_border, o, cfg.width, nullptr),
+             "me_remap_q5");
+      VL_TRY(me_remap_q5(tctx, ME_DEVICE, R, raw_w[1], raw_h[1], raw_w[1], (const int32_t*)rect_map[1], cfg.width,
+                         cfg.height, rect_border, o + npx, cfg.width, nullptr),
+             "me_remap_q5");
+    } else if (equalise && mem == ME_DEVICE) {  // (the caller's images are never written: equalised into the slot)
+      VL_TRY(me_clahe(tctx, ME_DEVICE, L, cfg.width, cfg.height, cfg.width, &eq_params, o, cfg.width, nullptr), "me_clahe");
+      VL_TRY(me_clahe(tctx, ME_DEVICE, R, cfg.width, cfg.height, cfg.width, &eq_params, o + npx, cfg.width, nullptr),
+             "me_clahe");
+      return ME_OK;
+    } else {
+      VL_TRY(me_memcpy_async(tctx, o, L, npx), "image upload");
+      VL_TRY(me_memcpy_async(tctx, o + npx, R, npx), "image upload");
+    }
+    if (equalise) {  // in place: the slot is the loop's
+      VL_TRY(me_clahe(tctx, ME_DEVICE, o, cfg.width, cfg.height, cfg.width, &eq_params, o, cfg.width, nullptr), "me_clahe");
+      VL_TRY(me_clahe(tctx, ME_DEVICE, o + npx, cfg.width, cfg.height, cfg.width, &eq_params, o + npx, cfg.width, nullptr),
+             "me_clahe");
+    }
+    return ME_OK;
+  }
+  // The state seeded from keyframe t's active tracks: their left positions, in the order the next klt_submit
+  // uploads them (table order)
+  int kf_seed(int t) {
+    const FrameObs& po = obs[t];
+    kf_ref.clear();
+    for (size_t i = 0; i < ntab(); ++i) {
+      if (!active[i]) continue;
+      const size_t pos = (size_t)(std::lower_bound(po.ids.begin(), po.ids.end(), ids[i]) - po.ids.begin());
+      kf_ref.push_back(po.feats[4 * pos]);
+      kf_ref.push_back(po.feats[4 * pos + 1]);
+    }
+    kf_n = (int)(kf_ref.size() / 2);
+    kf_gap = 0;
+    const size_t n = (size_t)kf_n;
+    void *hp, *d;
+    VL_TRY(dbuf("kf", kf_info_offset() + 32, &d), "kf");
+    if (n == 0) return ME_OK;
+    VL_TRY(hbuf("kf_in", 25 * n, &hp), "kf");
+    std::memcpy(hp, kf_ref.data(), 8 * n);
+    std::memcpy((uint8_t*)hp + 8 * n, kf_ref.data(), 8 * n);
+    std::memset((uint8_t*)hp + 24 * n, 1, n);
+    // (new_uv's bytes ride along in the one copy: the tracker writes them before they are read)
+    VL_TRY(me_memcpy_async(tctx, d, hp, 25 * n), "kf H2D");
+    return ME_OK;
+  }
+  // One pushed frame: the loop's tracker (not guided) pv -> cur at cur_uv, me_kf_update behind it, the info block back
+  int kf_track(const Imgs& pv, const Imgs& cur, unsigned char* info_out) {
+    const size_t n = (size_t)kf_n, o_info = kf_info_offset();
+    void *d, *ho;
+    VL_TRY(dbuf("kf", o_info + 32, &d), "kf");  // (sized by the seed: it does not grow here)
+    uint8_t* b = (uint8_t*)d;
+    if (n) {
+      me_klt_params kp;
+      me_klt_default_params(&kp);
+      if (cfg.klt_fb_max > 0.0)
+        VL_TRY(me_klt_track_fb(tctx, ME_DEVICE, pv.L, cur.L, cfg.width, cfg.height, cfg.width, (const float*)(b + 8 * n),
+                               (float*)(b + 16 * n), b + 25 * n, nullptr, (int)n, &kp, cfg.klt_fb_max),
+               "me_klt_track_fb");
+      else
+        VL_TRY(me_klt_track(tctx, ME_DEVICE, pv.L, cur.L, cfg.width, cfg.height, cfg.width, (const float*)(b + 8 * n),
+                            (float*)(b + 16 * n), b + 25 * n, (int)n, &kp),
+               "me_klt_track");
+    }
+    VL_TRY(me_kf_update(tctx, n ? (const float*)b : nullptr, n ? (float*)(b + 8 * n) : nullptr, n ? b + 24 * n : nullptr,
+                        n ? (const float*)(b + 16 * n) : nullptr, n ? b + 25 * n : nullptr, (int)n, cfg.width,
+                        cfg.height, (float)kMargin, kf_gap, &kf_params, b + o_info),
+           "me_kf_update");
+    VL_TRY(hbuf("kf_out", 32, &ho), "kf");
+    VL_TRY(me_memcpy_async(tctx, ho, b + o_info, 32), "kf D2H");
+    VL_TRY(me_synchronize(tctx), "kf_track");
+    std::memcpy(info_out, ho, 32);
+    return ME_OK;
+  }
+  // The keyframe tracker's guess: cur_uv of the alive features, the keyframe's positions of the others
+  int kf_read_guess(std::vector<float>& guess) {
+    const size_t n = (size_t)kf_n;
+    void *d, *ho;
+    VL_TRY(dbuf("kf", kf_info_offset() + 32, &d), "kf");
+    VL_TRY(hbuf("kf_state", 17 * n, &ho), "kf");
+    VL_TRY(me_memcpy_async(tctx, ho, (uint8_t*)d + 8 * n, 17 * n), "kf D2H");  // cur_uv | new_uv | alive
+    VL_TRY(me_synchronize(tctx), "kf_guess");
+    const float* cu = (const float*)ho;
+    const uint8_t* al = (const uint8_t*)ho + 16 * n;
+    guess.resize(2 * n);
+    for (size_t k = 0; k < n; ++k) {
+      guess[2 * k] = al[k] ? cu[2 * k] : kf_ref[2 * k];
+      guess[2 * k + 1] = al[k] ? cu[2 * k + 1] : kf_ref[2 * k + 1];
+    }
+    return ME_OK;
+  }
+  int push(const uint8_t* left, const uint8_t* right, me_mem mem, int* keyframe_t) {
+    *keyframe_t = -1;
+    int slot = 0;
+    while (slot == push_prev || slot == push_kf[0] || slot == push_kf[1]) ++slot;  // (three held at the most: < 4)
+    Imgs im;
+    VL_TRY(prepare_pushed(slot, left, right, mem, im), "images");
+    ++n_pushed;
+    std::vector<float> guess;
+    bool guided = false;
+    if (has_prev) {
+      ++kf_gap;
+      const Imgs pv = push_prev >= 0 ? push_imgs : imgs[prev_t];
+      alignas(8) unsigned char info[32] = {0};
+      VL_TRY(kf_track(pv, im, info), "kf_track");
+      int32_t flags;
+      std::memcpy(&flags, info + 12, 4);
+      if (flags == 0) {  // no keyframe: the frame becomes the previous pushed frame, nothing else moves
+        push_prev = slot;
+        push_imgs = im;
+        return ME_OK;
+      }
+      if (kf_gap >= 2 && kf_n > 0) {
+        VL_TRY(kf_read_guess(guess), "kf_guess");
+        guided = true;
+      }
+    }
+    const int t = has_prev ? prev_t + 1 : 0;
+    imgs[t] = im;  // (frame_images finds the keyframe's pair prepared)
+    kf_guess = guided ? &guess : nullptr;
+    const int rc = process(t, nullptr, nullptr, ME_DEVICE);
+    kf_guess = nullptr;
+    if (rc != ME_OK) return rc;
+    push_kf[1] = push_kf[0];
+    push_kf[0] = slot;
+    push_prev = -1;
+    VL_TRY(kf_seed(t), "kf_seed");
+    *keyframe_t = t;
     return ME_OK;
   }
   int finish() {
@@ -1648,6 +1821,10 @@ int me_vo_loop_set_tonemap(me_vo_loop* v, const me_tonemap_params* p) {
   }
   v->tonemap_off();
   if (!p) return ME_OK;
+  if (v->kf_on) {
+    v->err = "me_vo_loop_set_tonemap: the tone map together with keyframe selection is not supported";
+    return ME_ERR_INVALID;
+  }
   if (const char* why = me_tonemap_check(p)) {
     v->err = std::string("me_vo_loop_set_tonemap: ") + why;
     return ME_ERR_INVALID;
@@ -1657,8 +1834,55 @@ int me_vo_loop_set_tonemap(me_vo_loop* v, const me_tonemap_params* p) {
   return rc;
 }
 
+int me_vo_loop_set_keyframe_select(me_vo_loop* v, const me_kf_params* p) {
+  if (!v) return ME_ERR_INVALID;
+  if (p) {
+    if (const char* why = me_kf_check(p)) {
+      v->err = std::string("me_vo_loop_set_keyframe_select: ") + why;
+      return ME_ERR_INVALID;
+    }
+    if (v->tonemap) {
+      v->err = "me_vo_loop_set_keyframe_select: keyframe selection together with the tone map is not supported";
+      return ME_ERR_INVALID;
+    }
+  }
+  if (v->has_prev || v->failed) {
+    v->err = "me_vo_loop_set_keyframe_select: keyframe selection is set before the first frame";
+    return ME_ERR_STATE;
+  }
+  v->kf_on = p != nullptr;
+  if (p) v->kf_params = *p;
+  return ME_OK;
+}
+
+int me_vo_loop_push(me_vo_loop* v, const uint8_t* left, const uint8_t* right, me_mem mem, int* keyframe_t) {
+  if (!v || !left || !right || !keyframe_t) return ME_ERR_INVALID;
+  *keyframe_t = -1;
+  if (!v->kf_on) {
+    v->err = "me_vo_loop_push: camera frames need me_vo_loop_set_keyframe_select";
+    return ME_ERR_STATE;
+  }
+  if (v->failed) {
+    v->err = "me_vo_loop_push: an earlier call failed (" + v->err + "); the loop state is undefined";
+    return ME_ERR_STATE;
+  }
+  if (v->has_prev && v->n_pushed == 0) {
+    v->err = "me_vo_loop_push: this loop's keyframes come through me_vo_loop_process";
+    return ME_ERR_STATE;
+  }
+  v->depth = 8;
+  me_range range_("me_vo_loop_push");
+  const int rc = v->push(left, right, mem, keyframe_t);
+  if (rc != ME_OK) v->failed = true;
+  return rc;
+}
+
 int me_vo_loop_process(me_vo_loop* v, int t, const uint8_t* left, const uint8_t* right, me_mem mem) {
   if (!v || !left || !right) return ME_ERR_INVALID;
+  if (v->n_pushed > 0) {
+    v->err = "me_vo_loop_process: this loop's frames come through me_vo_loop_push";
+    return ME_ERR_STATE;
+  }
   if (t != (v->has_prev ? v->prev_t + 1 : 0)) {
     v->err = "me_vo_loop_process: keyframes must come in order 0, 1, 2, ...";
     return ME_ERR_STATE;

@@ -131,8 +131,16 @@ class PipelineConfig:
     equalise: "Clahe | None" = None  # equalise.Clahe: both images of a keyframe are equalised ahead of the tracker
     tonemap: "ToneMap | None" = None  # tonemap.ToneMap: process() takes uint16 images and reduces them to 8 bits first
     motion_gate: "MotionGate | None" = None  # motion_gate.MotionGate: tracks that do not move with the camera are dropped
+    keyframe_select: "KeyframeSelect | None" = None  # keyframe.KeyframeSelect: push() takes camera frames, picks keyframes
 
     def __post_init__(self):
+        if self.keyframe_select is not None:
+            from .keyframe import KeyframeSelect
+
+            if not isinstance(self.keyframe_select, KeyframeSelect):
+                raise ValueError("keyframe_select must be a keyframe.KeyframeSelect or None")
+            if self.tonemap is not None:  # (the tone map's temporal state per pushed frame is not defined)
+                raise ValueError("keyframe_select together with tonemap is not supported")
         if self.rectify is not None:
             from .rectify import StereoRectifier
 
@@ -421,9 +429,44 @@ class Backend:
     camera = None  # (f, cx, cy, baseline) of the loop, for the gate
     gate_log = None  # host backends: (t, info) of every gate run (motion_gate_ref's info dict)
     _gate_prev = None  # the previous keyframe's (u, v, x_r) of the features in flight (klt_submit's prev_xr)
+    keyframe_select = None  # PipelineConfig.keyframe_select of the loop's configuration (None: push() is refused)
+    _kf = None  # host backends: [ref_uv, cur_uv, alive] of the features seeded at the last keyframe
 
     def frame_images(self, t: int, left: np.ndarray, right: np.ndarray):
         raise NotImplementedError
+
+    def release(self, t):
+        """The images frame_images(t, ..) returned are no longer read."""
+
+    def adopt_images(self, key, t: int):
+        """The pushed frame whose images frame_images(key, ..) returned became keyframe t."""
+
+    # ---- keyframe selection (WindowedStereoVO.push; include/me_hip.h A12i)
+    def kf_seed(self, pts):
+        """The carried state seeded from a keyframe's active tracks (their left positions, upload order)."""
+        pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
+        self._kf = [pts.copy(), pts.copy(), np.ones(len(pts), np.uint8)]
+
+    def kf_track(self, prev, cur, gap: int) -> dict:
+        """One pushed frame: the loop's tracker (not guided) from the previous
+        pushed frame to this one at the carried positions, then the update and
+        the decision (keyframe.kf_update_ref); returns its info."""
+        from .keyframe import kf_update_ref
+
+        ref, cu, al = self._kf
+        if self.klt_fb_max > 0.0:
+            uv, st, _ = klt_fb_host(self.klt, prev, cur, cu, self.klt_fb_max)
+        else:
+            uv, st = self.klt(prev, cur, cu)
+        H, W = cur[2]
+        cu, al, info = kf_update_ref(ref, cu, al, uv, st, W, H, MARGIN, gap, self.keyframe_select)
+        self._kf = [ref, cu, al]
+        return info
+
+    def kf_guess(self) -> np.ndarray:
+        """The keyframe tracker's initial guess: the carried position of an alive feature, the keyframe's of a dead one."""
+        ref, cu, al = self._kf
+        return np.where(al[:, None] != 0, cu, ref)
 
     def rectified_pair(self, left, right):
         """The pair frame_images gets: a host backend (rectifies = False)
@@ -853,6 +896,78 @@ class GPUBackend(Backend):
         for raw in self._raw.pop(t, ()):  # the raw pair behind a rectified one
             if isinstance(raw, int):
                 self.tctx.free(raw)
+
+    def adopt_images(self, key, t):
+        if key in self._imgs:
+            self._imgs[t] = self._imgs.pop(key)
+        if key in self._raw:
+            self._raw[t] = self._raw.pop(key)
+
+    # ---- keyframe selection on the front-end context.  Device block "kf" of n seeded features:
+    # ref_uv (8n) | cur_uv (8n) | new_uv (8n) | alive (n) | status (n), the info block at the next 16-byte boundary
+    _kf_n = 0
+    _kf_ref = None
+
+    def _kf_block(self):
+        n = self._kf_n
+        o_info = 16 * ((26 * n + 15) // 16)
+        return self._dbuf("kf", o_info + 32), o_info
+
+    def kf_seed(self, pts):
+        pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
+        n = self._kf_n = len(pts)
+        self._kf_ref = pts.copy()
+        d, _ = self._kf_block()
+        if n == 0:
+            return
+        hp = self._hbuf("kf_in", 25 * n)
+        self._view(hp, np.float32, 2 * n)[:] = pts.ravel()
+        self._view(hp, np.float32, 2 * n, 8 * n)[:] = pts.ravel()
+        self._view(hp, np.uint8, n, 24 * n)[:] = 1
+        self.tctx.copy_async(d, hp, 25 * n)  # (new_uv's bytes ride along: the tracker writes them before they are read)
+
+    def kf_track(self, prev, cur, gap):
+        import ctypes
+
+        from ._lib import ME_DEVICE
+        from .keyframe import kf_update_device, parse_info
+        from .klt import klt_params
+
+        n = self._kf_n
+        H, W = cur[2]
+        c = self.tctx
+        d, o_info = self._kf_block()
+        V = ctypes.c_void_p
+        if n:
+            kp = klt_params()
+            if self.klt_fb_max > 0.0:
+                c.check(c.lib.me_klt_track_fb(c.h, ME_DEVICE, V(prev[0]), V(cur[0]), W, H, W, V(d + 8 * n), V(d + 16 * n),
+                                              V(d + 25 * n), None, n, ctypes.byref(kp), float(self.klt_fb_max)),
+                        "me_klt_track_fb")
+            else:
+                c.check(c.lib.me_klt_track(c.h, ME_DEVICE, V(prev[0]), V(cur[0]), W, H, W, V(d + 8 * n), V(d + 16 * n),
+                                           V(d + 25 * n), n, ctypes.byref(kp)), "me_klt_track")
+            kf_update_device(c, self.keyframe_select, d, d + 8 * n, d + 24 * n, d + 16 * n, d + 25 * n, n, W, H, MARGIN,
+                             gap, d + o_info)
+        else:
+            kf_update_device(c, self.keyframe_select, 0, 0, 0, 0, 0, 0, W, H, MARGIN, gap, d + o_info)
+        ho = self._hbuf("kf_out", 32)
+        c.copy_async(ho, d + o_info, 32)
+        c.synchronize()
+        return parse_info(self._view(ho, np.uint8, 32).copy())
+
+    def kf_guess(self):
+        n = self._kf_n
+        if n == 0:
+            return np.zeros((0, 2), np.float32)
+        c = self.tctx
+        d, _ = self._kf_block()
+        ho = self._hbuf("kf_state", 17 * n)
+        c.copy_async(ho, d + 8 * n, 17 * n)  # cur_uv | new_uv | alive
+        c.synchronize()
+        cu = self._view(ho, np.float32, 2 * n).reshape(n, 2)
+        al = self._view(ho, np.uint8, n, 16 * n)
+        return np.where(al[:, None] != 0, cu, self._kf_ref)
 
     def close(self):
         for st in self._tm_dev or ():
@@ -1431,6 +1546,11 @@ class WindowedStereoVO:
         self.be.equaliser = cfg.equalise
         self.be.tonemapper = cfg.tonemap
         self.be.motion_gate = cfg.motion_gate
+        self.be.keyframe_select = cfg.keyframe_select
+        # push(): frames pushed so far, frames since the last keyframe, the previous pushed frame's images and
+        # their key (None: a keyframe's), the images a keyframe's process() call finds prepared
+        self._n_pushed, self._kf_gap, self._kf_prev, self._kf_prev_key, self._prepared = 0, 0, None, None, None
+        self.kf_log = []  # per pushed frame: dict(frame, t (-1: no keyframe), gap, guided, n, m, rank, flags, med2)
         if hasattr(backend, "reserve"):
             backend.reserve(cfg)
         self.K = np.asarray(S.intrinsics(cfg.width, cfg.height) if K is None else K, np.float64)
@@ -1576,8 +1696,11 @@ class WindowedStereoVO:
         return r
 
     # ---------------------------------------------------------------- one keyframe
-    def process(self, t: int, left: np.ndarray, right: np.ndarray):
-        """Keyframe t.  The loop definition (both backends, overlap or not):
+    def process(self, t: int, left: np.ndarray, right: np.ndarray, guess=None):
+        """Keyframe t.  guess (push(): (n, 2) float32, one per active track in
+        upload order): the tracker of step 1 is the guided one and starts
+        there; it takes precedence over klt_predict's.  The loop definition
+        (both backends, overlap or not):
         the BA of keyframe t - 1 enters the state (poses, landmarks) only after
         keyframe t is matched and booked -- keyframe t's prediction, matching
         and new tracks use the state after BA(t - 2) -- so BA(t - 1) runs on
@@ -1600,6 +1723,7 @@ class WindowedStereoVO:
         t_in = time.perf_counter()
         w0 = self.stage_s["wait"]
         cfg = self.cfg
+        prepared, self._prepared = self._prepared, None
         if left is not None and np.asarray(left).dtype == np.uint16:  # 16-bit ingest: tone map -> remap -> CLAHE
             if cfg.tonemap is None:
                 raise ValueError("WindowedStereoVO.process: uint16 images need PipelineConfig.tonemap")
@@ -1608,7 +1732,8 @@ class WindowedStereoVO:
             left, right = self.be.rectified_pair(left, right)
         if self.be.equaliser is not None and left is not None:
             left, right = self.be.equalised_pair(left, right)
-        imgs = self.be.frame_images(t, left, right)
+        # (push(): the front-end chain ran already, on the frame that now is keyframe t)
+        imgs = prepared if prepared is not None else self.be.frame_images(t, left, right)
         # 1. KLT of the active tracks, queued first (it needs only frame t-1's features)
         kh = None
         if self.prev_imgs is not None and self.active.any():
@@ -1619,7 +1744,12 @@ class WindowedStereoVO:
             pos = np.arange(len(pid)) if len(aid) == len(pid) and np.array_equal(aid, pid) else np.searchsorted(pid, aid)
             # (the rigid-motion gate: the tracks' previous x_r rides up with the tracker's input)
             gkw = {} if cfg.motion_gate is None else {"prev_xr": np.ascontiguousarray(puv[pos, 2])}
-            if cfg.klt_predict:
+            if guess is not None:
+                guess = np.ascontiguousarray(guess, np.float32).reshape(-1, 2)
+                if len(guess) != len(act):
+                    raise ValueError(f"WindowedStereoVO.process: {len(guess)} guesses for {len(act)} active tracks")
+                kh = self.be.klt_submit(self.prev_imgs, imgs, np.ascontiguousarray(puv[pos, :2]), guess=guess, **gkw)
+            elif cfg.klt_predict:
                 # pose(t) ahead of step 3 (the pops in between change none of its inputs): each landmark's
                 # predicted pixel is where its search starts
                 guess = predict_uv(self.X[act], self._predict_pose(t), self.f, self.cx, self.cy)
@@ -1698,6 +1828,63 @@ class WindowedStereoVO:
         # 9. frame t-1's FrameResult (its scale LM result), while BA(t) runs
         self._complete_result(done)
         self.stage_s["host"] += (time.perf_counter() - t_in) - (self.stage_s["wait"] - w0)
+
+    def push(self, left: np.ndarray, right: np.ndarray) -> int:
+        """One camera frame (PipelineConfig.keyframe_select; include/me_hip.h
+        A12i and me_vo_loop_push).  Returns the keyframe index the frame became,
+        or -1.  The first frame is keyframe 0.  After keyframe t the carried
+        state is seeded from its active tracks (the order klt_submit uploads
+        them).  Every later frame: the front-end chain once, the backend's
+        kf_track (tracker from the previous pushed frame at the carried
+        positions, then the update and the decision).  Not a keyframe: the
+        frame becomes the previous pushed frame, nothing else moves.  A
+        keyframe: process() on the prepared images, guided by the carried
+        positions when at least one frame lay in between (gap >= 2); with
+        gap == 1 process() runs as it does without push()."""
+        cfg = self.cfg
+        if cfg.keyframe_select is None:
+            raise ValueError("WindowedStereoVO.push: needs PipelineConfig.keyframe_select")
+        if self.prev_t is not None and self._n_pushed == 0:
+            raise ValueError("WindowedStereoVO.push: this loop's keyframes come through process()")
+        if np.asarray(left).dtype == np.uint16:
+            raise ValueError("WindowedStereoVO.push: uint16 images are not supported (keyframe_select with tonemap)")
+        if self.be.rectifier is not None:
+            left, right = self.be.rectified_pair(left, right)
+        if self.be.equaliser is not None:
+            left, right = self.be.equalised_pair(left, right)
+        frame = self._n_pushed
+        key = ("push", frame)
+        imgs = self.be.frame_images(key, left, right)
+        self._n_pushed += 1
+        rec = dict(frame=frame, t=-1, gap=0, guided=False, n=0, m=0, rank=-1, flags=0, med2=0.0)
+        self.kf_log.append(rec)
+        guess = None
+        if self.prev_t is not None:
+            self._kf_gap += 1
+            info = self._wait(self.be.kf_track, self._kf_prev, imgs, self._kf_gap)
+            rec.update(gap=self._kf_gap, n=info["n"], m=info["m"], rank=info["rank"], flags=info["flags"],
+                       med2=info["med2"])
+            if self._kf_prev_key is not None:  # (the frame before this one was no keyframe: its images go)
+                self.be.release(self._kf_prev_key)
+            if not info["keyframe"]:
+                self._kf_prev, self._kf_prev_key = imgs, key
+                return -1
+            if self._kf_gap >= 2:
+                guess = self.be.kf_guess()
+        t = 0 if self.prev_t is None else self.prev_t + 1
+        self.be.adopt_images(key, t)
+        self._prepared = imgs
+        self.process(t, None, None, guess=guess)
+        rec.update(t=t, guided=guess is not None and len(guess) > 0)
+        self.be.release(t - 2)  # (KLT(t + 1) reads t's images; the scale LM of t - 1 ran inside process(t))
+        # the seed: the active tracks' left positions in keyframe t, in the order the next klt_submit uploads them
+        act = np.flatnonzero(self.active)
+        pid, puv = self.obs[t]
+        aid = self.ids[act]
+        pos = np.arange(len(pid)) if len(aid) == len(pid) and np.array_equal(aid, pid) else np.searchsorted(pid, aid)
+        self.be.kf_seed(np.ascontiguousarray(puv[pos, :2]))
+        self._kf_prev, self._kf_prev_key, self._kf_gap = imgs, None, 0
+        return t
 
     def finish(self):
         """Complete the last queued keyframe (its pops, scale LM, BA)."""
@@ -1891,16 +2078,19 @@ class WindowedStereoVO:
             self._tab_view()
 
 
-def synthetic_sequence(c: int, n_frames: int, seed: int | None = None, render_div: int = 1, first_id: int = 0):
+def synthetic_sequence(c: int, n_frames: int, seed: int | None = None, render_div: int = 1, first_id: int = 0,
+                       sub: int = 1):
     """Stereo keyframes of config c's synthetic sequence (0.5 m forward along
     the heading and 0.3 deg yaw per keyframe: the arc through the ring
     corridor, synthetic.trajectory_arc, any length), the true first pose and
     the per-frame motion prior used for the second keyframe.  first_id starts
-    the sequence at keyframe first_id of the arc (chunked long runs)."""
+    the sequence at keyframe first_id of the arc (chunked long runs).  sub > 1:
+    `sub` camera frames per keyframe step (frame i at first_id + i / sub; the
+    motion prior returned is then one camera frame's)."""
     cfg = S.CONFIGS[c]
     seed = S.SEED0 + c if seed is None else seed
     scene, K, frames = S.stereo_stream(seed, cfg["width"], cfg["height"], n_frames, first_id=first_id,
-                                       render_div=render_div, scene_kind="corridor")
+                                       render_div=render_div, scene_kind="corridor", sub=sub)
     poses = []
     for fr in frames:
         poses.append(np.concatenate([fr.t, S.R_to_aa_robust(fr.R)]))
@@ -1968,6 +2158,10 @@ class NativeStereoVO:
                 self._check(self.lib.me_vo_loop_set_motion_gate(self.h, ctypes.byref(gp)), "me_vo_loop_set_motion_gate")
             if cfg.klt_predict:
                 self._check(self.lib.me_vo_loop_set_klt_predict(self.h, 1), "me_vo_loop_set_klt_predict")
+            if cfg.keyframe_select is not None:
+                kc = cfg.keyframe_select.to_c()
+                self._check(self.lib.me_vo_loop_set_keyframe_select(self.h, ctypes.byref(kc)),
+                            "me_vo_loop_set_keyframe_select")
             if cfg.rectify is not None:  # the loop builds the two maps itself, on its front context
                 cl, cr = cfg.rectify.left.to_c(), cfg.rectify.right.to_c()
                 self._check(self.lib.me_vo_loop_set_rectify(self.h, ctypes.byref(cl), ctypes.byref(cr),
@@ -2060,6 +2254,51 @@ class NativeStereoVO:
             L, R = np.ascontiguousarray(L), np.ascontiguousarray(R)
             rc = entry(self.h, t, L.ctypes.data, R.ctypes.data, ME_HOST)
         self._check(rc, what)
+
+    def push(self, left, right) -> int:
+        """One camera frame through me_vo_loop_push (PipelineConfig.keyframe_select):
+        the keyframe index it became, or -1.  The input checks and the stream
+        ordering are process()'s; device tensors are kept referenced for two
+        pushes (the loop copies them on its stream during the call)."""
+        import ctypes
+
+        from ._lib import ME_DEVICE, ME_HOST
+
+        if self.cfg.keyframe_select is None:
+            raise ValueError("NativeStereoVO.push: needs PipelineConfig.keyframe_select")
+        shape = (self.cfg.height, self.cfg.width)
+        shapes = {"left": shape, "right": shape}
+        if self.cfg.rectify is not None:  # raw images: each camera model's own size
+            shapes = {"left": self.cfg.rectify.left.shape, "right": self.cfg.rectify.right.shape}
+        kt = ctypes.c_int(-1)
+        if hasattr(left, "data_ptr"):
+            import torch
+
+            for name, im in (("left", left), ("right", right)):
+                shape = shapes[name]
+                if not (isinstance(im, torch.Tensor) and im.dtype == torch.uint8 and tuple(im.shape) == shape
+                        and im.is_contiguous() and im.is_cuda and im.device.index == self.ctx.device):
+                    raise ValueError(f"NativeStereoVO.push: {name} must be a contiguous uint8 tensor of shape "
+                                     f"{shape} on cuda:{self.ctx.device}, got "
+                                     f"{getattr(im, 'dtype', None)} {tuple(getattr(im, 'shape', ()))} "
+                                     f"on {getattr(im, 'device', None)}")
+            self._order_after_torch(left.device)
+            self._pushed = getattr(self, "_pushed", 0) + 1
+            self._keep[("push", self._pushed)] = (left, right)
+            self._keep.pop(("push", self._pushed - 2), None)
+            rc = self.lib.me_vo_loop_push(self.h, ctypes.c_void_p(left.data_ptr()), ctypes.c_void_p(right.data_ptr()),
+                                          ME_DEVICE, ctypes.byref(kt))
+        else:
+            L, R = np.asarray(left), np.asarray(right)
+            for name, im in (("left", L), ("right", R)):
+                shape = shapes[name]
+                if im.dtype != np.uint8 or im.shape != shape:
+                    raise ValueError(f"NativeStereoVO.push: {name} must be a uint8 array of shape {shape}, got "
+                                     f"{im.dtype} {im.shape}")
+            L, R = np.ascontiguousarray(L), np.ascontiguousarray(R)
+            rc = self.lib.me_vo_loop_push(self.h, L.ctypes.data, R.ctypes.data, ME_HOST, ctypes.byref(kt))
+        self._check(rc, "me_vo_loop_push")
+        return int(kt.value)
 
     def finish(self):
         self._check(self.lib.me_vo_loop_finish(self.h), "me_vo_loop_finish")

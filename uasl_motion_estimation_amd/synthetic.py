@@ -362,15 +362,18 @@ def arc_radius(step: float = 0.5, yaw_deg: float = YAW_STEP_DEG) -> float:
     return step / (2.0 * math.sin(math.radians(yaw_deg) / 2.0))
 
 
-def trajectory_arc(n: int, first_id: int = 0):
+def trajectory_arc(n: int, first_id: int = 0, sub: int = 1):
     """World->camera poses (R, t) on the arc: heading psi = 0.3 deg k, camera
     forward (cos psi, -sin psi, 0), down (0, 0, -1), right (-sin psi, -cos psi,
     0) -- towards the circle's centre -- and centre C = R0 (sin psi, cos psi, 0)
-    + (0, 0, ARC_H)."""
+    + (0, 0, ARC_H).  sub > 1: frame i lies at k = first_id + i / sub, `sub`
+    frames per keyframe step (camera frames denser than the arc's keyframes)."""
+    if int(sub) < 1:
+        raise ValueError("sub must be >= 1")
     R0 = arc_radius()
     poses = []
     for i in range(n):
-        psi = math.radians(YAW_STEP_DEG) * (first_id + i)
+        psi = math.radians(YAW_STEP_DEG) * (first_id + i if sub == 1 else first_id + i / int(sub))
         c, s = math.cos(psi), math.sin(psi)
         Rw = np.array([[-s, 0.0, c], [-c, 0.0, -s], [0.0, -1.0, 0.0]])  # columns: right, down, forward
         C = np.array([R0 * s, R0 * c, ARC_H])
@@ -531,8 +534,9 @@ class StereoFrame:
 
 
 def stereo_stream(seed: int, width: int, height: int, n_frames: int, first_id: int = 0, render_div: int = 1,
-                  scene_kind: str = "strips"):
-    """Stereo keyframes of the synthetic trajectory.  render_div > 1 renders
+                  scene_kind: str = "strips", sub: int = 1):
+    """Stereo keyframes of the synthetic trajectory (sub > 1, corridor only:
+    `sub` camera frames per keyframe step, trajectory_arc).  render_div > 1 renders
     each image at 1/render_div resolution and replicates pixels (4K test
     inputs in seconds instead of minutes; the geometry -- intrinsics, poses,
     depth_at -- stays at full resolution).  scene_kind "corridor": the arc
@@ -554,7 +558,9 @@ def stereo_stream(seed: int, width: int, height: int, n_frames: int, first_id: i
         img = rf(scene, K_r, R, t, w_r, h_r, shift=shift)
         return np.ascontiguousarray(np.kron(img, np.ones((d, d), np.uint8))[:height, :width])
 
-    poses = list(trajectory_arc(n_frames, first_id) if corridor else trajectory(n_frames, first_id))
+    if sub != 1 and not corridor:
+        raise ValueError("sub needs scene_kind='corridor'")
+    poses = list(trajectory_arc(n_frames, first_id, sub) if corridor else trajectory(n_frames, first_id))
     jobs = [(R, t, sh) for (R, t) in poses for sh in (0.0, BASELINE)]
     # images are independent: rendered by a thread pool (numpy releases the GIL in the array work)
     workers = min(len(jobs), 16, os.cpu_count() or 1)
