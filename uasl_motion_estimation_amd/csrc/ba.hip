@@ -291,6 +291,39 @@ constexpr int kPtBlock = 64;   // per-point kernels: spread ~N/64 workgroups ove
 #endif
 constexpr int kLinSmall = ME_LIN_SMALL, kLinSmallMaxObs = 64 * 512;
 __host__ __device__ inline int lin_block(int no) { return no <= kLinSmallMaxObs ? kLinSmall : kBlock; }
+// One observation's pieces at the linearisation point: X = V_o (6 unique) |
+// g_o (3), W = W_o (6x3, only when `var`: a variable camera), returns the
+// observation's cost 0.5 rho0.  The one definition behind linearize_kernel and
+// the fused phase A of pt_schur_kernel: the same expressions, the same bits.
+template <int OD>
+__device__ __forceinline__ double lin_pieces(const Geo& g, const Bufs& b, long o, const double* cam, const double* pt,
+                                             bool var, double* X, double* W) {
+  double r[4], Jc[24], Jp[12];
+  obs_residual<OD>(g, b, o, cam, pt, r, Jc, Jp);
+  const double s = r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3];
+  double rho0, sc;
+  huber(s, &rho0, &sc);
+  for (int k = 0; k < 4; ++k) r[k] *= sc;
+  for (int k = 0; k < 24; ++k) Jc[k] *= sc;
+  for (int k = 0; k < 12; ++k) Jp[k] *= sc;
+  X[0] = Jp[0] * Jp[0] + Jp[3] * Jp[3] + Jp[6] * Jp[6] + Jp[9] * Jp[9];
+  X[1] = Jp[0] * Jp[1] + Jp[3] * Jp[4] + Jp[6] * Jp[7] + Jp[9] * Jp[10];
+  X[2] = Jp[0] * Jp[2] + Jp[3] * Jp[5] + Jp[6] * Jp[8] + Jp[9] * Jp[11];
+  X[3] = Jp[1] * Jp[1] + Jp[4] * Jp[4] + Jp[7] * Jp[7] + Jp[10] * Jp[10];
+  X[4] = Jp[1] * Jp[2] + Jp[4] * Jp[5] + Jp[7] * Jp[8] + Jp[10] * Jp[11];
+  X[5] = Jp[2] * Jp[2] + Jp[5] * Jp[5] + Jp[8] * Jp[8] + Jp[11] * Jp[11];
+  for (int a = 0; a < 3; ++a) X[6 + a] = Jp[a] * r[0] + Jp[3 + a] * r[1] + Jp[6 + a] * r[2] + Jp[9 + a] * r[3];
+  // (the camera normal-equation pieces are formed by cam_assemble from the
+  // same residual and Jacobian: no 216 B per observation through HBM)
+  if (var)
+    for (int a = 0; a < 6; ++a)
+      for (int c = 0; c < 3; ++c)
+        W[a * 3 + c] = Jc[a] * Jp[c] + Jc[6 + a] * Jp[3 + c] + Jc[12 + a] * Jp[6 + c] + Jc[18 + a] * Jp[9 + c];
+  return 0.5 * rho0;
+}
+
+// The separate linearisation launch: the Schur instances that do not
+// linearise in their phase A (schur_fused_lin) read its obsx / Wo.
 template <int OD, int BLK>
 __global__ __launch_bounds__(BLK) void linearize_kernel(Geo g, Bufs b) {
   __shared__ double lds[BLK / 64];
@@ -301,32 +334,10 @@ __global__ __launch_bounds__(BLK) void linearize_kernel(Geo g, Bufs b) {
   if (o < g.no) {
     const int cur = st->cur;
     const int ci = b.cam_idx[o], pi = b.pt_idx[o];
-    double r[4], Jc[24], Jp[12];
-    obs_residual<OD>(g, b, o, b.cams[cur] + 6 * ci, b.pts[cur] + 3 * pi, r, Jc, Jp);
-    const double s = r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3];
-    double rho0, sc;
-    huber(s, &rho0, &sc);
-    cost = 0.5 * rho0;
-    for (int k = 0; k < 4; ++k) r[k] *= sc;
-    for (int k = 0; k < 24; ++k) Jc[k] *= sc;
-    for (int k = 0; k < 12; ++k) Jp[k] *= sc;
     const long slot = b.pos[o];  // CSR-by-point slot: per-point stages read contiguously
-    double* X = b.obsx + slot * kObsxStride;
-    X[0] = Jp[0] * Jp[0] + Jp[3] * Jp[3] + Jp[6] * Jp[6] + Jp[9] * Jp[9];
-    X[1] = Jp[0] * Jp[1] + Jp[3] * Jp[4] + Jp[6] * Jp[7] + Jp[9] * Jp[10];
-    X[2] = Jp[0] * Jp[2] + Jp[3] * Jp[5] + Jp[6] * Jp[8] + Jp[9] * Jp[11];
-    X[3] = Jp[1] * Jp[1] + Jp[4] * Jp[4] + Jp[7] * Jp[7] + Jp[10] * Jp[10];
-    X[4] = Jp[1] * Jp[2] + Jp[4] * Jp[5] + Jp[7] * Jp[8] + Jp[10] * Jp[11];
-    X[5] = Jp[2] * Jp[2] + Jp[5] * Jp[5] + Jp[8] * Jp[8] + Jp[11] * Jp[11];
-    for (int a = 0; a < 3; ++a) X[6 + a] = Jp[a] * r[0] + Jp[3 + a] * r[1] + Jp[6 + a] * r[2] + Jp[9 + a] * r[3];
-    // (the camera normal-equation pieces are formed by cam_assemble from the
-    // same residual and Jacobian: no 216 B per observation through HBM)
-    if (ci - g.nf >= 0) {
-      double* W = b.Wo + 18 * slot;
-      for (int a = 0; a < 6; ++a)
-        for (int c = 0; c < 3; ++c)
-          W[a * 3 + c] = Jc[a] * Jp[c] + Jc[6 + a] * Jp[3 + c] + Jc[12 + a] * Jp[6 + c] + Jc[18 + a] * Jp[9 + c];
-    }
+    // (the pieces go straight to their slot of obsx / Wo)
+    cost = lin_pieces<OD>(g, b, o, b.cams[cur] + 6 * ci, b.pts[cur] + 3 * pi, ci - g.nf >= 0,
+                          b.obsx + slot * kObsxStride, b.Wo + 18 * slot);
   }
   double v[1] = {cost};
   double out[1];
@@ -627,7 +638,36 @@ constexpr int kSchurPts = 16, kSchurPtsWide = 32, kSchurPtsSmall = 8;
 #endif
 constexpr int kSchurNtMax = ME_SCHUR_NT;  // accumulator tiles per wave (3..5)
 constexpr size_t kSchurLdsCap = 150 * 1024;
+constexpr size_t kSchurLinLds = 8 * 9 * 512;  // fused linearisation: one cell of V_o | g_o sums per thread, behind the Y block
 __host__ __device__ inline size_t schur_lds_bytes(int P, int Rz) { return 8 * (size_t)3 * P * Rz + 4 * 3 * (size_t)P; }
+
+// Which pt_schur_kernel<OD, NT, 512, PTS> instances linearise in their phase A
+// (host and kernel read the same table).  An instance is fused when the
+// compiler's resource report keeps it within 256 VGPRs at 512 threads with no
+// more scratch than the unfused instance of the same NT
+// (profiles/fused_lin_resources.txt); the others keep the linearize_kernel
+// launch in front of them.
+// Both models alike: 2 and 3 tiles per wave fit with no scratch; 4 tiles keep
+// the unfused instance's 20 B with 16 and 32 landmarks per sub-chunk and take
+// 28 B with 8; 5 tiles take 64-84 B against 40-56.
+#ifndef ME_SCHUR_FUSED_NT
+#define ME_SCHUR_FUSED_NT 4  // most tiles per wave of a fused instance; 0: every instance unfused (A/B builds)
+#endif
+__host__ __device__ constexpr bool schur_fused_lin(int od, int nt, int pts) {
+  return (od == 4 || od == 2) && nt <= ME_SCHUR_FUSED_NT && (nt <= 3 || (nt == 4 && pts != kSchurPtsSmall));
+}
+__host__ __device__ constexpr int schur_nt(int stpw) {  // the instance's tile count for stpw = 8 waves x tiles
+  return stpw / 8 <= 2 ? 2 : stpw / 8 <= 3 ? 3 : stpw / 8 <= 4 ? 4 : 5;
+}
+
+// Before a lane reads back W_o words that lanes of its own wave stored earlier
+// in program order (fused linearisation): the wave's stores have reached the
+// memory its loads read (workgroup scope: one vector-memory wait, no cache
+// maintenance), and the loads are not moved ahead of it.
+__device__ __forceinline__ void own_stores_visible() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
 
 template <int W>
 __device__ __forceinline__ int group_min(int x) {
@@ -664,9 +704,10 @@ __device__ __forceinline__ int group_max(int x) {
   do {             \
   } while (0)
 #endif
-template <int NT, int BLK, int PTS>
+template <int OD, int NT, int BLK, int PTS>
 __global__ __launch_bounds__(BLK) void pt_schur_kernel(Geo g, Bufs b, Opts o, CamArgs ca) {
   constexpr int SL = BLK / PTS, NW = BLK / 64;  // lanes per landmark, waves
+  constexpr bool FL = schur_fused_lin(OD, NT, PTS);  // phase A linearises (no linearize_kernel launch, no obsx)
   extern __shared__ double smem[];
   __shared__ double red[8];
   // camera-assembly blocks of a fused launch come first: dispatched before the
@@ -679,10 +720,7 @@ __global__ __launch_bounds__(BLK) void pt_schur_kernel(Geo g, Bufs b, Opts o, Ca
 #ifdef ME_EXP_NOCAM  // timing experiment only (wrong results): the launch without its camera work, DESIGN §5.4's yardstick
     return;
 #endif
-    if (g.od == 4)
-      cam_assemble_body<4>(g, b, ca.cpart, 0, ca.colnorm, ca.gc_raw, ca.Uraw, q);
-    else
-      cam_assemble_body<2>(g, b, ca.cpart, 0, ca.colnorm, ca.gc_raw, ca.Uraw, q);
+    cam_assemble_body<OD>(g, b, ca.cpart, 0, ca.colnorm, ca.gc_raw, ca.Uraw, q);  // (this instance's model only)
     return;
   }
   const int sblk = (int)blockIdx.x - (ca.on ? ca.ncam : 0);  // this workgroup's index among the Schur runs
@@ -705,7 +743,8 @@ __global__ __launch_bounds__(BLK) void pt_schur_kernel(Geo g, Bufs b, Opts o, Ca
   // this workgroup's run and tile group; the run's tile set is [bA, bB] plus the z tile T - 1
   // Workgroups are dealt round-robin over the 8 XCDs: a run's tile groups sit
   // at blocks b, b + 8, ... so they share an XCD's L2 -- the second group's
-  // reads of the run's slots (W, obsx) hit the lines the first one fetched.
+  // reads of the run's slots (W, obsx; fused linearisation: the observations)
+  // hit the lines the first one fetched.
   const int sup = sblk / (8 * g.sgrp), r8 = sblk - sup * 8 * g.sgrp;
   const int run = 8 * sup + (r8 & 7), tgrp = r8 >> 3;
   if (run >= g.nruns) {  // (uniform) padding of the last block of 8 runs
@@ -723,6 +762,60 @@ __global__ __launch_bounds__(BLK) void pt_schur_kernel(Geo g, Bufs b, Opts o, Ca
   int* band = reinterpret_cast<int*>(Y + (size_t)rows * Rz);  // per landmark: first / last camera column, live
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int gi = tid / SL, gl = tid & (SL - 1);
+  // Fused linearisation (flin: this instance, a run of one sub-chunk in
+  // landmark order), ahead of everything else the workgroup sets up, so that
+  // little is live across it.  The run's landmarks are consecutive, so its CSR
+  // slots are one range [s0, s1): thread t takes slot s0 + t -- every lane
+  // busy, one pass whatever the track lengths -- and forms the slot's pieces
+  // (lin_pieces: linearize_kernel's expressions, the same bits).  W_o goes to
+  // b.Wo, where phase B and the later launches (pt_step_kernel, a
+  // need_lin == 0 pass) read it; V_o | g_o goes into the LDS cell of the lane
+  // that owns the slot in phase A (lane (q - beg) mod SL of the landmark's
+  // group), its slots q0, q0 + SL, ... added one round after the other: the
+  // order of phase A's obsx loop.  b.obsx is neither written nor read.
+  // EVERY tile group of the run does so, lead or not: the groups are
+  // workgroups of one launch that nothing orders, so a group never reads what
+  // another stored.  Each stores the same bits to the same words of b.Wo (a
+  // benign overlap) and reads back only what its own threads stored, behind
+  // own_stores_visible() and a workgroup barrier: race-free without any order
+  // between the groups.
+  // The camera of slot q is p_cam[q] + nf (== cam_idx[p_obs[q]]).
+  const bool flin = FL && g.flin && need_lin;
+  double* vl = reinterpret_cast<double*>(band + 3 * P);  // flin: [BLK][9], lane t's sum of V_o | g_o over its slots
+  __shared__ double cwave[NW];                           // per wave: 0.5 rho0 over its threads' slots
+  if constexpr (FL) {
+    if (flin) {
+      const int j0 = run * g.rlen;
+      const int s0 = b.p_off[j0], s1 = b.p_off[min(j0 + P, g.np)];
+      double cost = 0;
+      for (int base = s0; base < s1; base += BLK) {  // (uniform; one batch unless duplicates pile up)
+        const int q = base + tid;
+        int k = -1, cell = 0;
+        double X[9];
+        if (q < s1) {
+          const int ob = b.p_obs[q], ci = b.p_cam[q];
+          const int j = b.pt_idx[ob];
+          const int beg = b.p_off[j];
+          double xl[3], w[18];
+          for (int a = 0; a < 3; ++a) xl[a] = b.pts[cur][3 * (long)j + a];
+          const bool var = ci >= 0 && !final_pass;  // (no W_o for a fixed camera, nor for the closing pass)
+          cost += lin_pieces<OD>(g, b, ob, b.cams[cur] + 6 * (ci + g.nf), xl, var, X, w);
+          if (var)
+            for (int i = 0; i < 18; ++i) b.Wo[18 * (long)q + i] = w[i];
+          k = (q - beg) / SL;
+          cell = 9 * ((j - j0) * SL + ((q - beg) & (SL - 1)));
+        }
+        own_stores_visible();  // (before the barrier: the W_o stores of every wave have landed)
+        for (int r = 0;; ++r) {  // round r: the owning lanes' r-th slots, up to the batch's largest k (uniform exit)
+          if (k == r)
+            for (int i = 0; i < 9; ++i) vl[cell + i] = r == 0 ? X[i] : vl[cell + i] + X[i];
+          if (!__syncthreads_or(k > r)) break;
+        }
+      }
+      cost = wave_total(cost);
+      if (lane == 0) cwave[wave] = cost;  // (read by thread 0 behind the barriers of the sub-chunk loop)
+    }
+  }
   // this wave's tiles (wave-uniform: scalar registers): canonical index c of
   // the run's tile set (row ka of the set's upper triangle holds ns - ka pairs)
   int tI[NT], tJ[NT];
@@ -759,7 +852,7 @@ __global__ __launch_bounds__(BLK) void pt_schur_kernel(Geo g, Bufs b, Opts o, Ca
         ci0 = b.p_cam[q0];
         if (q0 > beg) cprev0 = b.p_cam[q0 - 1];
         if (q0 + 1 < end) cnext0 = b.p_cam[q0 + 1];  // duplicate test of phase B, requested with the rest
-        if (need_lin)
+        if (need_lin && !flin)
           for (int i = 0; i < 9; ++i) X0[i] = obsx[(long)q0 * kObsxStride + i];
         if (ci0 >= 0) {
           for (int i = 0; i < 18; ++i) w0[i] = Wo[18 * (long)q0 + i];
@@ -772,9 +865,13 @@ __global__ __launch_bounds__(BLK) void pt_schur_kernel(Geo g, Bufs b, Opts o, Ca
         if (scaled)
           for (int a = 0; a < 3; ++a) pv[a] = b.psc[3 * (long)j + a];
         double V[9];  // V_o (6 unique) | g_o (3)
-        for (int i = 0; i < 9; ++i) V[i] = X0[i];
-        for (int q = q0 + SL; q < end; q += SL)
-          for (int i = 0; i < 9; ++i) V[i] += obsx[(long)q * kObsxStride + i];
+        if (flin) {
+          for (int i = 0; i < 9; ++i) V[i] = q0 < end ? vl[9 * tid + i] : 0.0;  // (this lane's slots, summed ahead of the set-up)
+        } else {
+          for (int i = 0; i < 9; ++i) V[i] = X0[i];
+          for (int q = q0 + SL; q < end; q += SL)
+            for (int i = 0; i < 9; ++i) V[i] += obsx[(long)q * kObsxStride + i];
+        }
         SCHUR_T(1);  // loads of phase A issued and returned (first use)
       for (int i = 0; i < 9; ++i) V[i] = group_sum<SL>(V[i]);
         if (!scaled) {
@@ -966,6 +1063,11 @@ __global__ __launch_bounds__(BLK) void pt_schur_kernel(Geo g, Bufs b, Opts o, Ca
   if (need_lin) {
     const double r = block_max(gm, red);
     if (tid == 0) b.part[R_GMAX_PT * g.pstride + sblk] = r;
+    if (flin && lead && tid == 0) {  // the run's cost partial: the wave sums in wave order (g.ncost = nruns partials)
+      double c = 0;
+      for (int w = 0; w < NW; ++w) c += cwave[w];
+      b.part[R_COST * g.pstride + run] = c;
+    }
   }
   if (final_pass) return;
 #pragma unroll
@@ -1001,7 +1103,7 @@ __device__ void lin_finalize_body(const Geo& g, const Bufs& b, const Opts& o, co
     const bool in = t < kFinBlock;
     double c = 0, m = 0;
     if (!x && in) {
-      for (int i = t; i < g.nblk_lin; i += kFinBlock) c += b.part[R_COST * g.pstride + i];
+      for (int i = t; i < g.ncost; i += kFinBlock) c += b.part[R_COST * g.pstride + i];
       for (int i = t; i < g.ksplit; i += kFinBlock) m = fmax(m, b.part[R_GMAX_PT * g.pstride + i]);
     }
     const double* gcv = x ? b.xch + xo_gc(g) : gc_raw;
@@ -1053,7 +1155,7 @@ __device__ void xch_tail_body(const Geo& g, const Bufs& b, const double* gc_raw,
   const State* st = b.st;
   double c = 0, m = 0;
   if (st->need_lin) {
-    for (int i = threadIdx.x; i < g.nblk_lin; i += kFinBlock) c += b.part[R_COST * g.pstride + i];
+    for (int i = threadIdx.x; i < g.ncost; i += kFinBlock) c += b.part[R_COST * g.pstride + i];
     for (int i = threadIdx.x; i < g.ksplit; i += kFinBlock) m = fmax(m, b.part[R_GMAX_PT * g.pstride + i]);
   }
   double* x = b.xch;
@@ -3263,6 +3365,7 @@ struct Plan {
   int solve_flags = 0;  // cam_solve_kernel `flags`: the ctx's test-hook bits the kernel reads (kFlag*)
   int n_enq = 0;      // linearisations queued so far (the first runs the camera assembly on its own)
   bool no_fused_asm = false;  // test hook kFlagSeparateAsm: S assembly in its own launch
+  bool fused_lin = false;   // the plan's Schur instance linearises in its phase A: no linearize_kernel launch, no obsx
   bool full_S = false;      // assemble both block triangles of S (reduced-system / covariance read-back)
   int solve_cap = 0;        // co-resident cam_solve_kernel<2> workgroups on the ctx's CUs (0: not queried)
   me_comm* comm = nullptr;  // sharded solve: the exchange (null: one GPU)
@@ -3390,6 +3493,15 @@ int plan_build(me_ctx* c, const me_ba_problem* p, const me_ba_options* opt, Plan
   g.nblk_obs = (int)std::max(1L, rup(std::max(g.no, 1), kBlock) / kBlock);
   g.nblk_lin = (int)std::max(1L, rup(std::max(g.no, 1), lin_block(g.no)) / lin_block(g.no));
   g.nblk_pts = (int)std::max(1L, rup(std::max(g.np, 1), kPtBlock) / kPtBlock);
+  // (band-sorted runs and runs of several sub-chunks keep the separate launch: the fused phase takes one sub-chunk
+  // of consecutive landmarks; so do windows whose Y block leaves no LDS for its 512 x 9 sums)
+  // Every tile group of a run repeats the run's linearisation.  That costs no time while the launch's workgroups
+  // all run at once, one per CU (at most 128: the BA's half of the chip in the pipelined frame); a larger window
+  // with several groups per run keeps the separate launch, which linearises every observation once.
+  P.fused_lin = schur_fused_lin(g.od, schur_nt(g.stpw), g.spts) && g.rsub == 1 && !g.sorted &&
+                (g.sgrp == 1 || g.ksplit <= 128) && schur_lds_bytes(g.spts, g.Rpad) + kSchurLinLds <= kSchurLdsCap;
+  g.flin = P.fused_lin ? 1 : 0;
+  g.ncost = P.fused_lin ? g.nruns : g.nblk_lin;  // (nruns <= ksplit <= pstride)
   g.jacobi = opt->jacobi_scaling ? 1 : 0;
   // camera-assembly units launched: the per-camera counts of a device-resident problem are unknown here, so the
   // bound on sum max(1, ceil(n_c / 256)); the plan's unit table marks the units past the total
@@ -3443,7 +3555,7 @@ int plan_build(me_ctx* c, const me_ba_problem* p, const me_ba_options* opt, Plan
   add(4 * (size_t)g.no, &b.c_obs);
   add(4 * (size_t)g.no, &b.tmp_obs);
   add(4 * (size_t)g.no, &b.cpos);
-  add(8 * kObsxStride * (size_t)g.no, &b.obsx);
+  add(P.fused_lin ? 0 : 8 * kObsxStride * (size_t)g.no, &b.obsx);  // (fused: neither written nor read)
   add((size_t)g.no, &b.dup);
   add(8 * solve_a_doubles(g.Ts), &b.Abuf);
   add(8 * 18 * (size_t)g.no, &b.Wo);
@@ -3558,7 +3670,7 @@ int plan_build(me_ctx* c, const me_ba_problem* p, const me_ba_options* opt, Plan
   P.use_lds = solve_form(g.Ts) == 0 ? 1 : 0;
   P.solve_lds = 8 * (solve_small_doubles(g.Ts) + (P.use_lds ? solve_a_doubles(g.Ts) : 0));
   ME_CHECK(c, P.solve_lds <= kSolveLdsCap, "BA: %d variable cameras exceed the camera-solve workspace", g.m);
-  P.schur_lds = schur_lds_bytes(g.spts, g.Rpad);
+  P.schur_lds = schur_lds_bytes(g.spts, g.Rpad) + (P.fused_lin ? kSchurLinLds : 0);
   ME_CHECK(c, P.schur_lds <= kSchurLdsCap, "BA: %d variable cameras exceed the Schur workspace", g.m);
   // dynamic-LDS ceilings of the solve and Schur kernels: set once per context
   // at the cap every plan stays under (not per solve: ~36 runtime calls of
@@ -3566,10 +3678,11 @@ int plan_build(me_ctx* c, const me_ba_problem* p, const me_ba_options* opt, Plan
   if (!c->ba_lds_attr) {
     for (const void* k : {(const void*)cam_solve_kernel<0>, (const void*)cam_solve_kernel<1>, (const void*)cam_solve_kernel<2>})
       ME_HIP(c, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSolveLdsCap));
-#define ME_SCHUR_K(N)                                                                                   \
-  (const void*)pt_schur_kernel<N, 512, kSchurPts>, (const void*)pt_schur_kernel<N, 512, kSchurPtsWide>, \
-      (const void*)pt_schur_kernel<N, 512, kSchurPtsSmall>
-    for (const void* k : {ME_SCHUR_K(2), ME_SCHUR_K(3), ME_SCHUR_K(4), ME_SCHUR_K(5)})
+#define ME_SCHUR_K(D, N)                                                                                      \
+  (const void*)pt_schur_kernel<D, N, 512, kSchurPts>, (const void*)pt_schur_kernel<D, N, 512, kSchurPtsWide>, \
+      (const void*)pt_schur_kernel<D, N, 512, kSchurPtsSmall>
+    for (const void* k : {ME_SCHUR_K(4, 2), ME_SCHUR_K(4, 3), ME_SCHUR_K(4, 4), ME_SCHUR_K(4, 5), ME_SCHUR_K(2, 2),
+                          ME_SCHUR_K(2, 3), ME_SCHUR_K(2, 4), ME_SCHUR_K(2, 5)})
 #undef ME_SCHUR_K
       ME_HIP(c, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kSchurLdsCap));
     c->ba_lds_attr = 1;
@@ -3611,7 +3724,9 @@ int enqueue_linearize(Plan& P) {
   const Geo& g = P.g;
   hipStream_t s = c->stream;
   const bool sh = P.comm != nullptr;
-  {
+  // (no launch when the plan's Schur instance linearises in its phase A: the
+  // first pass is then cam_assemble -> Schur, every later one the Schur launch)
+  if (!P.fused_lin) {
     me_ktimer t(c, ME_KT_BA_LINEARIZE);
     const bool small = lin_block(g.no) == kLinSmall;
     if (g.od == 4 && small)
@@ -3655,24 +3770,28 @@ int enqueue_linearize(Plan& P) {
     // 120 B); wider windows take more tile groups per run instead.
     const int pw8 = g.stpw / 8;
     const dim3 grd(g.ksplit + ca.ncam);
-#define ME_SCHUR(N)                                                                                          \
-  do {                                                                                                       \
-    if (g.spts == kSchurPtsWide)                                                                             \
-      hipExtLaunchKernelGGL((pt_schur_kernel<N, 512, kSchurPtsWide>), grd, dim3(512), P.schur_lds, s, t.a, t.b, 0, g, \
-                            P.b, P.o, ca);                                                                   \
-    else if (g.spts == kSchurPtsSmall)                                                                       \
-      hipExtLaunchKernelGGL((pt_schur_kernel<N, 512, kSchurPtsSmall>), grd, dim3(512), P.schur_lds, s, t.a, t.b, 0, g, \
-                            P.b, P.o, ca);                                                                   \
-    else                                                                                                     \
-      hipExtLaunchKernelGGL((pt_schur_kernel<N, 512, kSchurPts>), grd, dim3(512), P.schur_lds, s, t.a, t.b, 0, g, P.b, \
-                            P.o, ca);                                                                        \
+#define ME_SCHUR_P(D, N, PTS) \
+  hipExtLaunchKernelGGL((pt_schur_kernel<D, N, 512, PTS>), grd, dim3(512), P.schur_lds, s, t.a, t.b, 0, g, P.b, P.o, ca)
+#define ME_SCHUR_D(D, N)                                                \
+  do {                                                                  \
+    if (g.spts == kSchurPtsWide) ME_SCHUR_P(D, N, kSchurPtsWide);       \
+    else if (g.spts == kSchurPtsSmall) ME_SCHUR_P(D, N, kSchurPtsSmall); \
+    else ME_SCHUR_P(D, N, kSchurPts);                                   \
+  } while (0)
+#define ME_SCHUR(N)                 \
+  do {                              \
+    if (g.od == 4) ME_SCHUR_D(4, N); \
+    else ME_SCHUR_D(2, N);          \
   } while (0)
     static_assert(kSchurNtMax >= 3 && kSchurNtMax <= 5, "instantiated tile counts");
+    static_assert(schur_nt(16) == 2 && schur_nt(24) == 3 && schur_nt(32) == 4 && schur_nt(40) == 5, "schur_nt is this dispatch");
     if (pw8 <= 2) ME_SCHUR(2);
     else if (pw8 <= 3) ME_SCHUR(3);
     else if (pw8 <= 4) ME_SCHUR(4);
     else ME_SCHUR(5);
 #undef ME_SCHUR
+#undef ME_SCHUR_D
+#undef ME_SCHUR_P
   }
   if (sh) {
     // this rank's reduced camera system, gradient and linearisation scalars

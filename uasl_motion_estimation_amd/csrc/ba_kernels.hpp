@@ -10,7 +10,9 @@
 //                  Jacobian (2-row residuals padded with zero rows, so every
 //                  later stage is shared), HuberLoss(1.0) corrector, cost;
 //                  stores only the normal-equation pieces (J^T J, J^T r
-//                  blocks), never the Jacobian itself.
+//                  blocks), never the Jacobian itself.  Small windows run
+//                  no such launch: pt_schur forms the pieces itself (its
+//                  fused linearisation, Geo::flin).
 //   cam_assemble   one workgroup per unit of 256 slots of a variable camera
 //                  (the plan's unit table), the last of a camera's to finish
 //                  reduces: Jacobi column norms (iteration 0), scaled
@@ -79,6 +81,8 @@ struct Geo {
   int nruns, rlen, rsub, sgrp, stpw, nblkp;
   int sorted;              // 0: runs in landmark order, every run takes the whole tile set (small windows)
   int od;                  // residual rows per observation: 4 StereoReprojectionError, 2 Standard/StereoRight
+  int flin;                // the Schur pass linearises in its phase A (no linearize_kernel launch, no obsx)
+  int ncost;               // cost partials per linearisation: nruns (the Schur pass linearises) or nblk_lin (linearize_kernel)
   int xslots, xrank;       // sharded: gradient max-norm slots in the exchange (one per rank) and this rank's
   double K0[9], K1[9];
   double baseline, sinv;
