@@ -1118,6 +1118,23 @@ class WindowedStereoVO {
   void setKeyframeSelect(const me_kf_params* params) {
     check(me_vo_loop_set_keyframe_select(v_.get(), params), "WindowedStereoVO::setKeyframeSelect");
   }
+  // Frame-rate pose output (me_hip.h A12j, me_vo_loop_set_frame_pose): with
+  // parameters every pushed frame after the first gets a pose relative to the
+  // last keyframe (framePoses()); nullptr switches it off (the default).  After
+  // setKeyframeSelect and before the first frame; otherwise, and for bad
+  // parameters, it throws.  The estimate is read only: keyframes and events are
+  // those of a loop without it.
+  void setFramePose(const me_frame_pose_params* params) {
+    check(me_vo_loop_set_frame_pose(v_.get(), params), "WindowedStereoVO::setFramePose");
+  }
+  // the frame poses of the pushed frames after the first, in push order (me_vo_loop_frame_poses)
+  std::vector<me_vo_frame_pose> framePoses() const {
+    int n = 0;
+    check(me_vo_loop_frame_poses(v_.get(), nullptr, 0, &n), "framePoses");
+    std::vector<me_vo_frame_pose> r((size_t)n);
+    check(me_vo_loop_frame_poses(v_.get(), r.data(), n, &n), "framePoses");
+    return r;
+  }
   // one camera frame (host images as in process(), copied in): the keyframe
   // index it became, or -1 (me_vo_loop_push)
   int push(const amd::ImageView& left, const amd::ImageView& right) {

@@ -96,7 +96,7 @@ int me_host_free(me_ctx* ctx, void* hptr);
 enum { ME_KT_MI = 0, ME_KT_SCALE_RES = 1, ME_KT_SCALE_NEQ = 2, ME_KT_BA_LINEARIZE = 3, ME_KT_BA_POINTS = 4,
        ME_KT_BA_SCHUR = 5, ME_KT_BA_SOLVE = 6, ME_KT_BA_STEP = 7, ME_KT_KLT = 8, ME_KT_PYR = 9, ME_KT_NMS = 10,
        ME_KT_CORNERS = 11, ME_KT_RECTIFY = 12, ME_KT_CLAHE = 13, ME_KT_TONEMAP = 14, ME_KT_GATE = 15,
-       ME_KT_KEYFRAME = 16, ME_KT_COUNT = 17, ME_KT_ALL = 0x1ffff };
+       ME_KT_KEYFRAME = 16, ME_KT_FRAMEPOSE = 17, ME_KT_COUNT = 18, ME_KT_ALL = 0x3ffff };
 int me_timing_enable(me_ctx* ctx, int family_mask);
 int me_timing_read(me_ctx* ctx, int kernel, long* launches, double* total_ms);
 int me_timing_reset(me_ctx* ctx);
@@ -587,6 +587,32 @@ int me_vo_loop_set_keyframe_select(me_vo_loop* v, const struct me_kf_params* p /
    A loop takes its frames through this entry or through me_vo_loop_process,
    not both: ME_ERR_STATE. */
 int me_vo_loop_push(me_vo_loop* v, const uint8_t* left, const uint8_t* right, me_mem mem, int* keyframe_t);
+/* Frame-rate pose output (A12j): with parameters every pushed frame after the
+   first, a frame that becomes a keyframe included, gets a pose relative to the
+   last keyframe.  The seed uploads the keyframe's x_r beside ref_uv (4 more
+   bytes per feature in the same copy) and zeroes the state's 128-byte pose
+   block, which sits directly behind the 32-byte keyframe block; me_frame_pose
+   is queued right behind me_kf_update on the same stream with start == info
+   (the previous frame's pose is the warm start, identity after a keyframe), and
+   one 160-byte copy stays the frame's one read-back.  The estimate is read
+   only: it feeds neither the keyframe decision, nor alive, nor the pose
+   prediction, so keyframes and events are those of a loop without it.  NULL
+   switches it off (the default: the loop makes exactly the calls it makes
+   without this setter).  Called after me_vo_loop_set_keyframe_select and
+   before the first frame: ME_ERR_INVALID otherwise, and for bad parameters
+   (me_frame_pose's rules).  A setter: me_vo_loop_config and ME_ABI_VERSION
+   stay as they are. */
+struct me_frame_pose_params; /* defined in section A12j below */
+int me_vo_loop_set_frame_pose(me_vo_loop* v, const struct me_frame_pose_params* p /* NULL: off */);
+/* The frame poses of the pushed frames after the first, in push order
+   (*n = their number; min(cap, *n) copied).  t: the keyframe index the frame
+   became, or -1; t_ref: the keyframe (R, t) is relative to; gap: frames since
+   it; the counts and valid of A12j's info block; X_frame = R X_t_ref + t. */
+typedef struct me_vo_frame_pose {
+  int32_t frame, t, t_ref, gap, n_usable, n_inliers, steps, valid;
+  double R[9], t_rel[3];
+} me_vo_frame_pose;
+int me_vo_loop_frame_poses(me_vo_loop* v, me_vo_frame_pose* out, int cap, int* n);
 /* Completes the last keyframe (its pops, scale LM and BA). */
 int me_vo_loop_finish(me_vo_loop* v);
 /* Results of the completed keyframes (*n = their number; min(cap, *n) copied). */
@@ -1154,6 +1180,66 @@ void me_kf_default_params(me_kf_params* p);
 int  me_kf_update(me_ctx* ctx, const float* ref_uv, float* cur_uv, uint8_t* alive, const float* new_uv,
                   const uint8_t* status, int n, int width, int height, float margin, int gap,
                   const me_kf_params* params, void* info);
+
+/* ---- A12j: frame pose, a pose-only refinement of every pushed frame
+ * (build-defined; no reference symbol).  The rigid motion (R, t) that takes
+ * points from the last keyframe's left-camera frame into the current frame's
+ * (Y = R P + t), from the keyframe's stereo observations ref_uv (n x 2 float)
+ * and ref_xr (n float) and the current frame's left-image positions cur_uv
+ * (n x 2 float) with their alive bytes: the state me_kf_update carries, plus
+ * the keyframe's x_r.  No RANSAC: an iteratively reweighted (Huber)
+ * Gauss-Newton from a start pose, then an inlier count.
+ *
+ * A12h's rules: integer and FP64 + - * / sqrt only, never contracted, every
+ * expression evaluated as written; frame_pose.frame_pose_ref restates this in
+ * numpy and reproduces every output bit for bit.  Per feature k with
+ * (u0, v0) = ref_uv_k, x0 = ref_xr_k, (u1, v1) = cur_uv_k:
+ *  1. usable_k iff alive_k != 0 && isfinite(u1) && isfinite(v1) &&
+ *     d0 >= min_disp with d0 = (double)u0 - (double)x0.
+ *  2. P_k as A12h step 3: fb = f * baseline, Z = fb / d0,
+ *     x = ((double)u0 - cx) * Z / f, y = ((double)v0 - cy) * Z / f.
+ *  3. start pose: `start` non-NULL points at an info block of this call; its
+ *     R, t are taken iff its valid word is 1.  Otherwise identity and zero.
+ *     start == info is allowed: the block is read before it is written.
+ *  4. the step, `iters` times, skipped altogether when fewer than 3 features
+ *     are usable.  Under the current pose Y as A12h step 6,
+ *     uh = f * Y_0 / Y_2 + cx, vh = f * Y_1 / Y_2 + cy,
+ *     r = (uh - (double)u1, vh - (double)v1), e2 = r0 r0 + r1 r1;
+ *     act_k iff usable_k && Y_2 > 0.  e = sqrt(e2); w = 1.0 if e <= huber,
+ *     else huber / e.  g_0, g_1 and the Jacobian rows J_m = (Y x g_m, g_m),
+ *     m = 0, 1, exactly as A12h step 8 (no third row).
+ *     H_ij = w * (J_0i J_0j + J_1i J_1j) for i <= j, row-major, and
+ *     b_i = w * (J_0i r_0 + J_1i r_1).  The 27 sums in A12h's order: a partial
+ *     per chunk of 64 consecutive feature indices, from +0.0, in index order (a
+ *     slot that is not act adds +0.0), then the partials in chunk order, from
+ *     +0.0.  H d = -b by the same Cholesky; a pivot that is not > 0 ends the
+ *     iterations and keeps the pose (NaN lands here too).  The same Cayley
+ *     update R <- C R, t <- C t + dt.  steps counts the completed updates.
+ *  5. final pass under the final pose: act and e2 as in 4,
+ *     g2 = gate_max * gate_max, inlier iff act && e2 <= g2.
+ *     valid = 1 iff steps == iters && n_inliers >= min_inliers.
+ *     err_out_k (n floats, may be NULL) = (float)sqrt(e2) for act features,
+ *     +inf otherwise.
+ *  6. info (128 bytes, 8-byte aligned): int32 n_usable, n_act (final pass),
+ *     n_inliers, steps, valid, three zero words, then R (row-major) and t as 12
+ *     doubles: the final estimate whether valid or not, the start pose when no
+ *     step ran.
+ * The defaults (1.0, 2.0, 0.5, 6, 6) come from a prototype on synthetic
+ * points, not from real data.  A parameter outside its range or not finite
+ * (huber, gate_max, min_disp finite and > 0; iters 0 .. 16; min_inliers >= 3),
+ * f or baseline not finite or <= 0, cx or cy not finite, n < 0 or n > 2^24, a
+ * null array with n > 0 and a null info are ME_ERR_INVALID; n = 0 is allowed
+ * (info alone is written, valid = 0).  Device memory, asynchronous on the ctx
+ * stream; timed in the ME_KT_FRAMEPOSE family.  Launches: see csrc/frame_pose.hip. */
+typedef struct me_frame_pose_params {
+  double huber, gate_max, min_disp;   /* pixels; all finite and > 0 */
+  int iters, min_inliers;             /* 0 .. 16; >= 3 */
+} me_frame_pose_params;
+void me_frame_pose_default_params(me_frame_pose_params* p);
+int  me_frame_pose(me_ctx* ctx, const float* ref_uv, const float* ref_xr, const float* cur_uv,
+                   const uint8_t* alive, int n, double f, double cx, double cy, double baseline,
+                   const me_frame_pose_params* params, const void* start /* may be NULL */,
+                   float* err_out /* may be NULL */, void* info /* 128 bytes, 8-aligned */);
 
 /* ---- A11: non-maximum suppression ------------------------------------
  * Replaces std::vector<pt2D> me::nonMaxSupScanline3x3(const cv::Mat& input,

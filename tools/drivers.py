@@ -44,6 +44,12 @@ loads another build of libme_hip.so (tools/build_variant.sh).
                          me_motion_gate on 2000 synthetic stereo tracks at 1280x720 (a fifth on a second body, 0.25 px
                          noise, the default parameters): HIP-event time of its three launches and the wall time per
                          call, and the config-3 native loop with the gate off / on, alternating
+  frame_pose [--reps --repeats --check --trace --loop N]
+                         me_frame_pose on 2000 synthetic features at 1280x720 (a fifth gross outliers, 0.3 px noise,
+                         the default parameters): HIP-event time of a call's seven launches and the wall time per
+                         call, me_kf_update and me_motion_gate on the same features beside it, and a config-3 push loop over N camera frames (three per keyframe
+                         step of the arc) with the frame pose off / on, alternating.  --trace 1: the calls alone,
+                         no event timing (the run rocprofv3 --kernel-trace --stats wraps)
 """
 import argparse
 import ctypes
@@ -1417,6 +1423,145 @@ def cmd_motion_gate(a):
     print(json.dumps(out))
 
 
+def cmd_frame_pose(a):
+    """me_frame_pose alone (ME_KT_FRAMEPOSE events: seven launches per call) and inside the config-3 native push loop."""
+    import torch
+
+    from uasl_motion_estimation_amd import frame_pose as FP
+    from uasl_motion_estimation_amd import keyframe as KF
+    from uasl_motion_estimation_amd import motion_gate as MG
+    from uasl_motion_estimation_amd import pipeline as PL
+    from uasl_motion_estimation_amd import synthetic as S
+
+    ctx = _setup(a.lib)
+    W, H, N = 1280, 720, 2000
+    f, cx, cy, b = 0.9 * W, W / 2.0, H / 2.0, S.BASELINE
+    rng = np.random.default_rng(11)
+    Z = rng.uniform(3.0, 40.0, N)
+    u, v = rng.uniform(30, W - 30, N), rng.uniform(30, H - 30, N)
+    P = np.stack([(u - cx) * Z / f, (v - cy) * Z / f, Z], 1)
+    Q = P @ S.aa_to_R(np.array([0.004, -0.02, 0.002])).T + np.array([0.03, -0.01, -0.5])
+
+    def proj(X):
+        return np.stack([f * X[:, 0] / X[:, 2] + cx, f * X[:, 1] / X[:, 2] + cy, f * (X[:, 0] - b) / X[:, 2] + cx], 1)
+
+    ref = (proj(P) + rng.normal(0, 0.3, (N, 3))).astype(np.float32)
+    cur = (proj(Q) + rng.normal(0, 0.3, (N, 3))).astype(np.float32)
+    gross = rng.random(N) < 0.2
+    cur[gross, :2] += rng.uniform(-40, 40, (int(gross.sum()), 2)).astype(np.float32)
+    ones = np.ones(N, np.uint8)
+    p = FP.FramePose()
+    out = {"inputs": f"{W}x{H}, {N} features, {int(gross.sum())} gross outliers, 0.3 px noise, defaults, start NULL",
+           "reps": a.reps, "calls": []}
+    # ref_uv | ref_xr | cur_uv | cur_xr | new_uv | alive | status | ok | ok_out | info (128) + kf info (32) |
+    # me_kf_update's own cur_uv and alive (it updates them in place: the pose's inputs stay what they are)
+    parts = [np.ascontiguousarray(ref[:, :2]), np.ascontiguousarray(ref[:, 2]), np.ascontiguousarray(cur[:, :2]),
+             np.ascontiguousarray(cur[:, 2]), np.ascontiguousarray(cur[:, :2]), ones, ones, ones, ones,
+             np.zeros(128 + 32, np.uint8), np.ascontiguousarray(cur[:, :2]), ones]
+    offs = [int(16 * ((x + 15) // 16)) for x in np.cumsum([0] + [q.nbytes + 16 for q in parts])]
+    host = np.zeros(offs[-1], np.uint8)
+    for q, o in zip(parts, offs):
+        host[o:o + q.nbytes] = q.view(np.uint8).ravel()
+    d = ctx.malloc(host.nbytes)
+    ctx.h2d(d, host)
+    o = [d + x for x in offs]
+    gp, kp = MG.MotionGate(), KF.KeyframeSelect()
+
+    def pose_call():
+        FP.frame_pose_device(ctx, p, o[0], o[1], o[2], o[5], N, f, cx, cy, b, o[9])
+
+    def kf_call():
+        KF.kf_update_device(ctx, kp, o[0], o[10], o[11], o[4], o[6], N, W, H, PL.MARGIN, 1, o[9] + 128)
+
+    def gate_call():
+        MG.motion_gate_device(ctx, gp, o[0], o[1], o[2], o[3], o[6], o[7], N, f, cx, cy, b, W, H, PL.MARGIN, 7, o[8])
+
+    if a.trace:
+        for _ in range(a.reps):
+            pose_call()
+            kf_call()
+            gate_call()
+        ctx.synchronize()
+        ctx.free(d)
+        print(json.dumps({"traced_calls": a.reps}))
+        return
+    for rep_ in range(a.repeats):
+        rows = [("me_frame_pose", "FRAMEPOSE", 1 + p.iters, pose_call), ("me_kf_update", "KEYFRAME", 1, kf_call),
+                ("me_motion_gate", "GATE", 3, gate_call)]
+        for name, fam, per, call in rows:
+            for _ in range(5):
+                call()
+            ctx.synchronize()
+            w0 = time.perf_counter()
+            for _ in range(a.reps):
+                call()
+            ctx.synchronize()
+            wall = (time.perf_counter() - w0) / a.reps * 1e6  # (no event timing in this window)
+            ctx.timing(True, [fam])
+            ctx.timing_reset()
+            for _ in range(a.reps):
+                call()
+            ctx.synchronize()
+            ctx.timing(False)
+            cnt, ms = ctx.timing_read(fam)
+            r = {"call": name, "repeat": rep_,
+                 "wall_us_per_call": round(wall, 2), f"{fam}_us_per_call": round(1000 * ms / max(cnt // per, 1), 2),
+                 f"{fam}_launches_timed": cnt}
+            out["calls"].append(r)
+            print(json.dumps(r), flush=True)
+    ctx.free(d)
+    if a.check:
+        err, info = FP.frame_pose_ref(ref, cur[:, :2], ones, f, cx, cy, b, p)
+        gerr, ginfo = FP.frame_pose(ref, cur[:, :2], ones, f, cx, cy, b, p, ctx=ctx)
+        same = (np.array_equal(gerr.view(np.uint32), err.view(np.uint32))
+                and np.array_equal(ginfo["words"], FP.info_words(info)))
+        out.update(n_usable=info["n_usable"], n_inliers=info["n_inliers"], steps=info["steps"], valid=info["valid"])
+        print(f"frame_pose parity vs the restatement: {'bit-exact' if same else 'MISMATCH'} (usable "
+              f"{info['n_usable']}, inliers {info['n_inliers']}, steps {info['steps']}, valid {info['valid']}, "
+              f"t {[round(float(x), 4) for x in info['t']]})", flush=True)
+        if not same:
+            sys.exit(1)
+    if a.loop > 0:
+        c, NF, SUB = 3, a.loop, 3
+        poses = S.trajectory_arc(NF, sub=SUB)
+        truth = [np.concatenate([t, S.R_to_aa_robust(R)]) for (R, t) in poses]
+        K = S.intrinsics(1280, 720)
+        scene = S.CorridorScene(S.SEED0 + c, S.arc_radius())
+        lut = torch.as_tensor(S.tone_map(), device="cuda")
+        frames = []
+        for (R, t) in poses:
+            L = S.render_corridor_torch(scene, K, R, t, 1280, 720, 0.0, "cuda")
+            Rr = lut[S.render_corridor_torch(scene, K, R, t, 1280, 720, S.BASELINE, "cuda").long()]
+            frames.append((L.contiguous(), Rr.contiguous()))
+        torch.cuda.synchronize()
+        print(f"rendered {len(frames)} camera frames, {SUB} per keyframe step of the arc", flush=True)
+        vel = SUB * (truth[1] - truth[0])  # per keyframe step; the loop's prediction is not scaled by the gap
+        runs = []
+        for rep_ in range(-1, a.repeats):  # (-1: a short untimed run, the first loop of a process pays the allocations)
+            for on in (False, True):
+                cfg = PL.PipelineConfig.from_config(c, keyframe_select=kp, frame_pose=p if on else None)
+                vo = PL.NativeStereoVO(cfg, ctx, K, truth[0], vel, log_events=False, overlap=True)
+                t0 = time.perf_counter()
+                nf = NF if rep_ >= 0 else min(NF, 30)
+                kts = [vo.push(*frames[i]) for i in range(nf)]
+                vo.finish()
+                dt = time.perf_counter() - t0
+                log = vo.frame_pose_log if on else []
+                vo.close()
+                if rep_ < 0:
+                    continue
+                nk = sum(1 for t in kts if t >= 0)
+                r = {"frame_pose": on, "repeat": rep_, "frames": nf, "keyframes": nk, "frames_per_s": round(nf / dt, 2),
+                     "keyframes_per_s": round(nk / dt, 2)}
+                if on:
+                    r.update(poses=len(log), valid=sum(q["pose_valid"] for q in log),
+                             inliers_mean=round(float(np.mean([q["n_inliers"] for q in log])), 1))
+                runs.append(r)
+                print(json.dumps(r), flush=True)
+        out["push_loop_config3"] = runs
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--lib", default=os.environ.get("ME_LIB"))
@@ -1485,6 +1630,12 @@ def main():
     p.add_argument("--repeats", type=int, default=3)
     p.add_argument("--check", type=int, default=1)
     p.add_argument("--loop", type=int, default=200, help="keyframes of the config-3 native loop per run (0: skip)")
+    p = sub.add_parser("frame_pose")
+    p.add_argument("--reps", type=int, default=200)
+    p.add_argument("--repeats", type=int, default=3)
+    p.add_argument("--check", type=int, default=1)
+    p.add_argument("--trace", type=int, default=0, help="1: the calls alone, no event timing (under rocprofv3)")
+    p.add_argument("--loop", type=int, default=200, help="camera frames of the config-3 native push loop per run (0: skip)")
     a = ap.parse_args()
     globals()["cmd_" + a.cmd](a)
 

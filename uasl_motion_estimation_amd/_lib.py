@@ -39,7 +39,7 @@ ERRORS = {
 KT = dict(MI=0, SCALE_RES=1, SCALE_NEQ=2, BA_LINEARIZE=3, BA_POINTS=4, BA_SCHUR=5, BA_SOLVE=6, BA_STEP=7,
           KLT=8, PYR=9, NMS=10, CORNERS=11, RECTIFY=12, CLAHE=13, TONEMAP=14, GATE=15)
 # families from 16 on (tests/test_rectify.py pins KT's values below 16): timing() / timing_read() take these names too
-KT_MORE = dict(KEYFRAME=16)
+KT_MORE = dict(KEYFRAME=16, FRAMEPOSE=17)
 
 
 class MEError(RuntimeError):
@@ -176,6 +176,19 @@ class KfParamsC(ctypes.Structure):
     _fields_ = [("min_parallax", c_double), ("min_tracked_pct", c_int), ("max_gap", c_int)]
 
 
+class FramePoseParamsC(ctypes.Structure):
+    """me_frame_pose_params (include/me_hip.h)."""
+    _fields_ = [("huber", c_double), ("gate_max", c_double), ("min_disp", c_double), ("iters", c_int),
+                ("min_inliers", c_int)]
+
+
+class VoFramePoseC(ctypes.Structure):
+    """me_vo_frame_pose (include/me_hip.h)."""
+    _fields_ = [("frame", ctypes.c_int32), ("t", ctypes.c_int32), ("t_ref", ctypes.c_int32), ("gap", ctypes.c_int32),
+                ("n_usable", ctypes.c_int32), ("n_inliers", ctypes.c_int32), ("steps", ctypes.c_int32),
+                ("valid", ctypes.c_int32), ("R", c_double * 9), ("t_rel", c_double * 3)]
+
+
 class ClaheParamsC(ctypes.Structure):
     """me_clahe_params (include/me_hip.h)."""
     _fields_ = [("tiles_x", c_int), ("tiles_y", c_int), ("clip_limit", c_double)]
@@ -217,6 +230,7 @@ EXPORTS = [
     "me_motion_gate_default_params", "me_motion_gate", "me_vo_loop_set_motion_gate",
     "me_vo_loop_set_klt_predict",
     "me_kf_default_params", "me_kf_update", "me_vo_loop_set_keyframe_select", "me_vo_loop_push",
+    "me_frame_pose_default_params", "me_frame_pose", "me_vo_loop_set_frame_pose", "me_vo_loop_frame_poses",
 ]
 
 class MonoParamsC(ctypes.Structure):
@@ -390,6 +404,11 @@ def load_library(path: str | None = None):
                                  c_float, c_int, P(KfParamsC), c_void_p]),
         "me_vo_loop_set_keyframe_select": (c_int, [c_void_p, P(KfParamsC)]),
         "me_vo_loop_push": (c_int, [c_void_p, c_void_p, c_void_p, c_int, P(c_int)]),
+        "me_frame_pose_default_params": (None, [P(FramePoseParamsC)]),
+        "me_frame_pose": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_double,
+                                  c_double, c_double, P(FramePoseParamsC), c_void_p, c_void_p, c_void_p]),
+        "me_vo_loop_set_frame_pose": (c_int, [c_void_p, P(FramePoseParamsC)]),
+        "me_vo_loop_frame_poses": (c_int, [c_void_p, P(VoFramePoseC), c_int, P(c_int)]),
         "me_tonemap_default_params": (None, [P(ToneMapParamsC)]),
         "me_tonemap_state_create": (c_int, [c_void_p, P(c_void_p)]),
         "me_tonemap_state_destroy": (c_int, [c_void_p]),
@@ -544,7 +563,7 @@ class Context:
         """Enable HIP-event timing of every kernel family, or only of `families` (names of KT)."""
         mask = 0
         if on:
-            mask = 0x1FFFF if families is None else sum(1 << {**KT, **KT_MORE}[f] for f in families)
+            mask = 0x3FFFF if families is None else sum(1 << {**KT, **KT_MORE}[f] for f in families)
         self.check(self.lib.me_timing_enable(self.h, mask))
 
     def timing_sample(self, every: int):

@@ -70,6 +70,7 @@ struct me_ctx {
   long scale_counters[4] = {0, 0, 0, 0};  // last solve: residual / normal-equation evaluations, LM rejections, executed residual evaluations
   // MI term tables, one per patch pixel count N (built on first use, mi.hip)
   float* mi_table[256] = {nullptr};
+  bool fpose_armed = false;  // the work block of me_frame_pose holds zeroed tickets and counters (frame_pose.hip)
   bool tonemap_armed = false;  // the stateless block of me_tonemap16 holds zeroed tables and tickets (tonemap.hip)
 };
 
@@ -120,6 +121,8 @@ const char* me_clahe_check(const me_clahe_params* p, int width, int height);
 const char* me_tonemap_check(const me_tonemap_params* p);
 // me_motion_gate's parameter checks (motion_gate.hip): NULL, or the message naming the argument.
 const char* me_motion_gate_check(const me_motion_gate_params* p);
+// me_frame_pose's parameter checks (frame_pose.hip): NULL, or the message naming the argument.
+const char* me_frame_pose_check(const me_frame_pose_params* p);
 // me_kf_update's parameter checks (keyframe.hip): NULL, or the message naming the argument.
 const char* me_kf_check(const me_kf_params* p);
 
@@ -147,6 +150,6 @@ enum {
   SLOT_IMG_L = 0, SLOT_IMG_R, SLOT_XY_L, SLOT_XY_R, SLOT_MI_OUT, SLOT_RED, SLOT_GENERIC,
   SLOT_SC_TRACKS, SLOT_SC_RES, SLOT_SC_RES2, SLOT_SC_NEQ, SLOT_SC_IMGL, SLOT_SC_IMGR,
   SLOT_KLT_PYR, SLOT_KLT_PTS, SLOT_NMS, SLOT_VO, SLOT_EPI, SLOT_MONO, SLOT_CORNERS,
-  SLOT_RECTIFY, SLOT_CLAHE, SLOT_TONEMAP, SLOT_TONEMAP_WORK, SLOT_GATE,
+  SLOT_RECTIFY, SLOT_CLAHE, SLOT_TONEMAP, SLOT_TONEMAP_WORK, SLOT_GATE, SLOT_FPOSE, SLOT_FPOSE_WORK,
   SLOT_COUNT
 };

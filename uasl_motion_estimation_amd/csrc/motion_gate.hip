@@ -21,9 +21,12 @@
 // library is built with -ffp-contract=off.
 #include <cmath>
 #include <cstdint>
+#include "gate_math.hpp"
 #include "me_internal.hpp"
 
 namespace {
+
+using namespace me_gate;  // cross3, dot3, reproject, gn_update
 
 constexpr int kBlock = 256;       // threads of every kernel here
 constexpr int kWaves = kBlock / 64;
@@ -68,13 +71,6 @@ __device__ __forceinline__ uint32_t lowbias32(uint32_t x) {
   return x;
 }
 
-__device__ __forceinline__ void cross3(const double* a, const double* b, double* c) {
-  c[0] = a[1] * b[2] - a[2] * b[1];
-  c[1] = a[2] * b[0] - a[0] * b[2];
-  c[2] = a[0] * b[1] - a[1] * b[0];
-}
-__device__ __forceinline__ double dot3(const double* a, const double* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-
 // Orthonormal frame of the triangle with edges a, b: false when it is degenerate
 __device__ __forceinline__ bool frame3(const double* a, const double* b, double* e1, double* e2, double* e3) {
   const double aa = dot3(a, a), bb = dot3(b, b);
@@ -89,19 +85,6 @@ __device__ __forceinline__ bool frame3(const double* a, const double* b, double*
   }
   cross3(e3, e1, e2);
   return true;
-}
-
-// Y = R P + t, the three residuals and their squared norm
-__device__ __forceinline__ void reproject(const double* R, const double* t, const double* P, double u, double v,
-                                          double xr, const GateArgs& g, double* Y, double* r, double& e2) {
-  for (int i = 0; i < 3; ++i) Y[i] = ((R[3 * i] * P[0] + R[3 * i + 1] * P[1]) + R[3 * i + 2] * P[2]) + t[i];
-  const double uh = g.f * Y[0] / Y[2] + g.cx;
-  const double vh = g.f * Y[1] / Y[2] + g.cy;
-  const double xh = uh - g.fb / Y[2];
-  r[0] = uh - u;
-  r[1] = vh - v;
-  r[2] = xh - xr;
-  e2 = (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2];
 }
 
 __global__ __launch_bounds__(kBlock) void gate_prep_kernel(GateArgs g) {
@@ -209,34 +192,6 @@ __global__ __launch_bounds__(kBlock) void gate_count_kernel(GateArgs g) {
   }
 }
 
-// x with A x = b, A 6 x 6 symmetric (full storage), by a textbook Cholesky; false at the first pivot not > 0
-__device__ bool cholesky6(const double (*A)[6], const double* b, double* x) {
-  double L[6][6];
-  for (int j = 0; j < 6; ++j) {
-    double s = A[j][j];
-    for (int k = 0; k < j; ++k) s = s - L[j][k] * L[j][k];
-    if (!(s > 0.0)) return false;
-    L[j][j] = sqrt(s);
-    for (int i = j + 1; i < 6; ++i) {
-      s = A[i][j];
-      for (int k = 0; k < j; ++k) s = s - L[i][k] * L[j][k];
-      L[i][j] = s / L[j][j];
-    }
-  }
-  double y[6];
-  for (int i = 0; i < 6; ++i) {
-    double s = b[i];
-    for (int k = 0; k < i; ++k) s = s - L[i][k] * y[k];
-    y[i] = s / L[i][i];
-  }
-  for (int i = 5; i >= 0; --i) {
-    double s = y[i];
-    for (int k = i + 1; k < 6; ++k) s = s - L[k][i] * x[k];
-    x[i] = s / L[i][i];
-  }
-  return true;
-}
-
 __global__ __launch_bounds__(kBlock) void gate_finish_kernel(GateArgs g) {
   __shared__ double s_stage[kWaves][kSums][kChunk + 1];  // (+1: a lane per sum reads its row without bank conflicts)
   __shared__ double s_tot[kSums];
@@ -331,40 +286,7 @@ __global__ __launch_bounds__(kBlock) void gate_finish_kernel(GateArgs g) {
       }
       __syncthreads();
       if (tid == 0) {
-        double A[6][6], b[6], d[6];
-        int s = 0;
-        for (int i = 0; i < 6; ++i)
-          for (int j = i; j < 6; ++j) {
-            A[i][j] = s_tot[s];
-            A[j][i] = s_tot[s];
-            ++s;
-          }
-        for (int i = 0; i < 6; ++i) b[i] = -s_tot[21 + i];
-        if (!cholesky6(A, b, d)) {
-          s_stop = 1;
-        } else {
-          // Cayley rotation of c = w / 2, then R <- C R, t <- C t + dt
-          const double c[3] = {0.5 * d[0], 0.5 * d[1], 0.5 * d[2]};
-          const double cc = (c[0] * c[0] + c[1] * c[1]) + c[2] * c[2];
-          const double den = 1.0 + cc, om = 1.0 - cc;
-          double C[9];
-          C[0] = (om + 2.0 * (c[0] * c[0])) / den;
-          C[4] = (om + 2.0 * (c[1] * c[1])) / den;
-          C[8] = (om + 2.0 * (c[2] * c[2])) / den;
-          C[1] = (2.0 * (c[0] * c[1]) - 2.0 * c[2]) / den;
-          C[2] = (2.0 * (c[0] * c[2]) + 2.0 * c[1]) / den;
-          C[3] = (2.0 * (c[1] * c[0]) + 2.0 * c[2]) / den;
-          C[5] = (2.0 * (c[1] * c[2]) - 2.0 * c[0]) / den;
-          C[6] = (2.0 * (c[2] * c[0]) - 2.0 * c[1]) / den;
-          C[7] = (2.0 * (c[2] * c[1]) + 2.0 * c[0]) / den;
-          double Rn[9], tn[3];
-          for (int i = 0; i < 3; ++i) {
-            for (int j = 0; j < 3; ++j) Rn[3 * i + j] = (C[3 * i] * R[j] + C[3 * i + 1] * R[3 + j]) + C[3 * i + 2] * R[6 + j];
-            tn[i] = ((C[3 * i] * t[0] + C[3 * i + 1] * t[1]) + C[3 * i + 2] * t[2]) + d[3 + i];
-          }
-          for (int i = 0; i < 9; ++i) s_pose[i] = Rn[i];
-          for (int i = 0; i < 3; ++i) s_pose[9 + i] = tn[i];
-        }
+        if (!gn_update(s_tot, s_pose)) s_stop = 1;  // (H d = -b, the Cayley update: gate_math.hpp)
       }
       __syncthreads();
       if (s_stop) break;  // (uniform)

@@ -223,6 +223,11 @@ struct me_vo_loop {
   long n_pushed = 0;
   std::vector<float> kf_ref;  // the seeded features' positions in the last keyframe
   void* push_slot[4] = {nullptr, nullptr, nullptr, nullptr};
+  // the frame pose (me_vo_loop_set_frame_pose, me_hip.h A12j): the block becomes ref_uv | cur_uv | new_uv |
+  // ref_xr (4n) | alive | status, and the 128-byte pose block sits directly behind the 32-byte info block
+  bool fpose = false;
+  me_frame_pose_params fpose_params{};
+  std::vector<me_vo_frame_pose> fposes;  // per pushed frame after the first
   int push_prev = -1, push_kf[2] = {-1, -1};  // slots of the previous pushed frame (-1: a keyframe), the last two keyframes
   const std::vector<float>* kf_guess = nullptr;  // set around process(): the tracker's guess, ahead of klt_predict's
   double f = 0, cx = 0, cy = 0;
@@ -1497,7 +1502,9 @@ struct me_vo_loop {
     return ME_OK;
   }
   // ------------------------------------------------------------ me_vo_loop_push (pipeline.WindowedStereoVO.push)
-  size_t kf_info_offset() const { return 16 * ((26 * (size_t)kf_n + 15) / 16); }
+  size_t kf_info_offset() const { return 16 * (((fpose ? 30 : 26) * (size_t)kf_n + 15) / 16); }
+  size_t kf_info_bytes() const { return fpose ? 160 : 32; }  // the keyframe block, and the pose block behind it
+  size_t kf_alive_offset() const { return (fpose ? 28 : 24) * (size_t)kf_n; }  // alive (n), then status (n)
   // The front-end chain of one pushed frame, once, into push_slot[slot]: upload or copy, remap, CLAHE
   int prepare_pushed(int slot, const uint8_t* L, const uint8_t* R, me_mem mem, Imgs& im) {
     const size_t npx = (size_t)cfg.width * cfg.height;
@@ -1551,7 +1558,26 @@ struct me_vo_loop {
     kf_gap = 0;
     const size_t n = (size_t)kf_n;
     void *hp, *d;
-    VL_TRY(dbuf("kf", kf_info_offset() + 32, &d), "kf");
+    VL_TRY(dbuf("kf", kf_info_offset() + kf_info_bytes(), &d), "kf");
+    if (fpose) {
+      // one copy of the whole block: x_r rides beside the positions, the pose block behind the info block is
+      // zeroed (valid = 0: the first frame after the keyframe starts at identity)
+      const size_t total = kf_info_offset() + 160;
+      VL_TRY(hbuf("kf_in", total, &hp), "kf");
+      std::memset(hp, 0, total);
+      std::memcpy(hp, kf_ref.data(), 8 * n);
+      std::memcpy((uint8_t*)hp + 8 * n, kf_ref.data(), 8 * n);
+      float* xr = (float*)((uint8_t*)hp + 24 * n);
+      size_t k = 0;
+      for (size_t i = 0; i < ntab(); ++i) {
+        if (!active[i]) continue;
+        const size_t pos = (size_t)(std::lower_bound(po.ids.begin(), po.ids.end(), ids[i]) - po.ids.begin());
+        xr[k++] = po.feats[4 * pos + 2];
+      }
+      std::memset((uint8_t*)hp + 28 * n, 1, n);
+      VL_TRY(me_memcpy_async(tctx, d, hp, total), "kf H2D");
+      return ME_OK;
+    }
     if (n == 0) return ME_OK;
     VL_TRY(hbuf("kf_in", 25 * n, &hp), "kf");
     std::memcpy(hp, kf_ref.data(), 8 * n);
@@ -1563,42 +1589,48 @@ struct me_vo_loop {
   }
   // One pushed frame: the loop's tracker (not guided) pv -> cur at cur_uv, me_kf_update behind it, the info block back
   int kf_track(const Imgs& pv, const Imgs& cur, unsigned char* info_out) {
-    const size_t n = (size_t)kf_n, o_info = kf_info_offset();
+    const size_t n = (size_t)kf_n, o_info = kf_info_offset(), o_al = kf_alive_offset(), nb = kf_info_bytes();
     void *d, *ho;
-    VL_TRY(dbuf("kf", o_info + 32, &d), "kf");  // (sized by the seed: it does not grow here)
+    VL_TRY(dbuf("kf", o_info + nb, &d), "kf");  // (sized by the seed: it does not grow here)
     uint8_t* b = (uint8_t*)d;
     if (n) {
       me_klt_params kp;
       me_klt_default_params(&kp);
       if (cfg.klt_fb_max > 0.0)
         VL_TRY(me_klt_track_fb(tctx, ME_DEVICE, pv.L, cur.L, cfg.width, cfg.height, cfg.width, (const float*)(b + 8 * n),
-                               (float*)(b + 16 * n), b + 25 * n, nullptr, (int)n, &kp, cfg.klt_fb_max),
+                               (float*)(b + 16 * n), b + o_al + n, nullptr, (int)n, &kp, cfg.klt_fb_max),
                "me_klt_track_fb");
       else
         VL_TRY(me_klt_track(tctx, ME_DEVICE, pv.L, cur.L, cfg.width, cfg.height, cfg.width, (const float*)(b + 8 * n),
-                            (float*)(b + 16 * n), b + 25 * n, (int)n, &kp),
+                            (float*)(b + 16 * n), b + o_al + n, (int)n, &kp),
                "me_klt_track");
     }
-    VL_TRY(me_kf_update(tctx, n ? (const float*)b : nullptr, n ? (float*)(b + 8 * n) : nullptr, n ? b + 24 * n : nullptr,
-                        n ? (const float*)(b + 16 * n) : nullptr, n ? b + 25 * n : nullptr, (int)n, cfg.width,
+    VL_TRY(me_kf_update(tctx, n ? (const float*)b : nullptr, n ? (float*)(b + 8 * n) : nullptr, n ? b + o_al : nullptr,
+                        n ? (const float*)(b + 16 * n) : nullptr, n ? b + o_al + n : nullptr, (int)n, cfg.width,
                         cfg.height, (float)kMargin, kf_gap, &kf_params, b + o_info),
            "me_kf_update");
-    VL_TRY(hbuf("kf_out", 32, &ho), "kf");
-    VL_TRY(me_memcpy_async(tctx, ho, b + o_info, 32), "kf D2H");
+    if (fpose)  // right behind the update, from the previous frame's pose (start == info)
+      VL_TRY(me_frame_pose(tctx, n ? (const float*)b : nullptr, n ? (const float*)(b + 24 * n) : nullptr,
+                           n ? (const float*)(b + 8 * n) : nullptr, n ? b + o_al : nullptr, (int)n, cfg.K[0], cfg.K[2],
+                           cfg.K[5], cfg.baseline, &fpose_params, b + o_info + 32, nullptr, b + o_info + 32),
+             "me_frame_pose");
+    VL_TRY(hbuf("kf_out", nb, &ho), "kf");
+    VL_TRY(me_memcpy_async(tctx, ho, b + o_info, nb), "kf D2H");
     VL_TRY(me_synchronize(tctx), "kf_track");
-    std::memcpy(info_out, ho, 32);
+    std::memcpy(info_out, ho, nb);
     return ME_OK;
   }
   // The keyframe tracker's guess: cur_uv of the alive features, the keyframe's positions of the others
   int kf_read_guess(std::vector<float>& guess) {
     const size_t n = (size_t)kf_n;
     void *d, *ho;
-    VL_TRY(dbuf("kf", kf_info_offset() + 32, &d), "kf");
-    VL_TRY(hbuf("kf_state", 17 * n, &ho), "kf");
-    VL_TRY(me_memcpy_async(tctx, ho, (uint8_t*)d + 8 * n, 17 * n), "kf D2H");  // cur_uv | new_uv | alive
+    VL_TRY(dbuf("kf", kf_info_offset() + kf_info_bytes(), &d), "kf");
+    const size_t nb = kf_alive_offset() - 7 * n;  // cur_uv | new_uv | (ref_xr |) alive
+    VL_TRY(hbuf("kf_state", nb, &ho), "kf");
+    VL_TRY(me_memcpy_async(tctx, ho, (uint8_t*)d + 8 * n, nb), "kf D2H");
     VL_TRY(me_synchronize(tctx), "kf_guess");
     const float* cu = (const float*)ho;
-    const uint8_t* al = (const uint8_t*)ho + 16 * n;
+    const uint8_t* al = (const uint8_t*)ho + nb - n;
     guess.resize(2 * n);
     for (size_t k = 0; k < n; ++k) {
       guess[2 * k] = al[k] ? cu[2 * k] : kf_ref[2 * k];
@@ -1618,10 +1650,26 @@ struct me_vo_loop {
     if (has_prev) {
       ++kf_gap;
       const Imgs pv = push_prev >= 0 ? push_imgs : imgs[prev_t];
-      alignas(8) unsigned char info[32] = {0};
+      alignas(8) unsigned char info[160] = {0};
       VL_TRY(kf_track(pv, im, info), "kf_track");
       int32_t flags;
       std::memcpy(&flags, info + 12, 4);
+      if (fpose) {  // the record: relative to the keyframe the state was seeded from; nothing below reads it
+        me_vo_frame_pose r{};
+        int32_t w[5];
+        std::memcpy(w, info + 32, 20);
+        r.frame = (int32_t)(n_pushed - 1);
+        r.t = flags != 0 ? prev_t + 1 : -1;
+        r.t_ref = prev_t;
+        r.gap = kf_gap;
+        r.n_usable = w[0];
+        r.n_inliers = w[2];
+        r.steps = w[3];
+        r.valid = w[4];
+        std::memcpy(r.R, info + 64, 72);
+        std::memcpy(r.t_rel, info + 64 + 72, 24);
+        fposes.push_back(r);
+      }
       if (flags == 0) {  // no keyframe: the frame becomes the previous pushed frame, nothing else moves
         push_prev = slot;
         push_imgs = im;
@@ -1852,6 +1900,40 @@ int me_vo_loop_set_keyframe_select(me_vo_loop* v, const me_kf_params* p) {
   }
   v->kf_on = p != nullptr;
   if (p) v->kf_params = *p;
+  if (!p) v->fpose = false;  // (the frame pose refines pushed frames: it goes with the switch it needs)
+  return ME_OK;
+}
+
+int me_vo_loop_set_frame_pose(me_vo_loop* v, const me_frame_pose_params* p) {
+  if (!v) return ME_ERR_INVALID;
+  if (p) {
+    if (const char* why = me_frame_pose_check(p)) {
+      v->err = std::string("me_vo_loop_set_frame_pose: ") + why;
+      return ME_ERR_INVALID;
+    }
+    if (!v->kf_on) {
+      v->err = "me_vo_loop_set_frame_pose: the frame pose needs me_vo_loop_set_keyframe_select first";
+      return ME_ERR_INVALID;
+    }
+    if (!(std::isfinite(v->cfg.baseline) && v->cfg.baseline > 0.0)) {
+      v->err = "me_vo_loop_set_frame_pose: baseline must be finite and > 0";
+      return ME_ERR_INVALID;
+    }
+  }
+  if (v->has_prev || v->n_pushed > 0) {
+    v->err = "me_vo_loop_set_frame_pose: the frame pose is set before the first frame";
+    return ME_ERR_INVALID;
+  }
+  v->fpose = p != nullptr;
+  if (p) v->fpose_params = *p;
+  return ME_OK;
+}
+
+int me_vo_loop_frame_poses(me_vo_loop* v, me_vo_frame_pose* out, int cap, int* n) {
+  if (!v || !n) return ME_ERR_INVALID;
+  *n = (int)v->fposes.size();
+  if (out)
+    for (int i = 0; i < std::min(cap, *n); ++i) out[i] = v->fposes[(size_t)i];
   return ME_OK;
 }
 

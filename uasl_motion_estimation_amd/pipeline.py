@@ -132,6 +132,7 @@ class PipelineConfig:
     tonemap: "ToneMap | None" = None  # tonemap.ToneMap: process() takes uint16 images and reduces them to 8 bits first
     motion_gate: "MotionGate | None" = None  # motion_gate.MotionGate: tracks that do not move with the camera are dropped
     keyframe_select: "KeyframeSelect | None" = None  # keyframe.KeyframeSelect: push() takes camera frames, picks keyframes
+    frame_pose: "FramePose | None" = None  # frame_pose.FramePose: every pushed frame gets a pose relative to the last keyframe
 
     def __post_init__(self):
         if self.keyframe_select is not None:
@@ -141,6 +142,15 @@ class PipelineConfig:
                 raise ValueError("keyframe_select must be a keyframe.KeyframeSelect or None")
             if self.tonemap is not None:  # (the tone map's temporal state per pushed frame is not defined)
                 raise ValueError("keyframe_select together with tonemap is not supported")
+        if self.frame_pose is not None:
+            from .frame_pose import FramePose
+
+            if not isinstance(self.frame_pose, FramePose):
+                raise ValueError("frame_pose must be a frame_pose.FramePose or None")
+            if self.keyframe_select is None:
+                raise ValueError("frame_pose needs keyframe_select (push() is what it refines)")
+            if not (math.isfinite(self.baseline) and self.baseline > 0.0):
+                raise ValueError("frame_pose: baseline must be finite and > 0")
         if self.rectify is not None:
             from .rectify import StereoRectifier
 
@@ -178,6 +188,12 @@ class PipelineConfig:
     def from_config(c: int, **kw) -> "PipelineConfig":
         cfg = S.CONFIGS[c]
         return PipelineConfig(cfg["width"], cfg["height"], cfg["n_feats"], cfg["window"], **kw)
+
+
+def compose_frame_pose(kf_pose, R_rel, t_rel):
+    """World -> camera (R, t) of a frame from its keyframe's pose {t, angle-axis} and the motion from it."""
+    R_rel, t_rel = np.asarray(R_rel, np.float64).reshape(3, 3), np.asarray(t_rel, np.float64).reshape(3)
+    return R_rel @ aa_to_R(kf_pose[3:]), R_rel @ np.asarray(kf_pose[:3], np.float64) + t_rel
 
 
 def check_rectifier_K(cfg: "PipelineConfig", K):
@@ -431,6 +447,9 @@ class Backend:
     _gate_prev = None  # the previous keyframe's (u, v, x_r) of the features in flight (klt_submit's prev_xr)
     keyframe_select = None  # PipelineConfig.keyframe_select of the loop's configuration (None: push() is refused)
     _kf = None  # host backends: [ref_uv, cur_uv, alive] of the features seeded at the last keyframe
+    frame_pose = None  # PipelineConfig.frame_pose of the loop's configuration (None: pushed frames get no pose)
+    _kf_xr = None  # host backends: the seeded features' x_r in the last keyframe (frame pose)
+    _kf_pose = None  # host backends: the previous pushed frame's pose info (None after a keyframe: identity start)
 
     def frame_images(self, t: int, left: np.ndarray, right: np.ndarray):
         raise NotImplementedError
@@ -442,15 +461,20 @@ class Backend:
         """The pushed frame whose images frame_images(key, ..) returned became keyframe t."""
 
     # ---- keyframe selection (WindowedStereoVO.push; include/me_hip.h A12i)
-    def kf_seed(self, pts):
-        """The carried state seeded from a keyframe's active tracks (their left positions, upload order)."""
+    def kf_seed(self, pts, xr=None):
+        """The carried state seeded from a keyframe's active tracks (their left
+        positions, upload order); xr: their x_r in the keyframe, which the frame pose triangulates with."""
         pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
         self._kf = [pts.copy(), pts.copy(), np.ones(len(pts), np.uint8)]
+        self._kf_xr = None if xr is None else np.ascontiguousarray(xr, np.float32).reshape(-1).copy()
+        self._kf_pose = None
 
     def kf_track(self, prev, cur, gap: int) -> dict:
         """One pushed frame: the loop's tracker (not guided) from the previous
         pushed frame to this one at the carried positions, then the update and
-        the decision (keyframe.kf_update_ref); returns its info."""
+        the decision (keyframe.kf_update_ref); returns its info.  With the
+        frame pose on, frame_pose.frame_pose_ref runs behind it from the
+        previous frame's pose and its info goes under "pose"."""
         from .keyframe import kf_update_ref
 
         ref, cu, al = self._kf
@@ -461,6 +485,13 @@ class Backend:
         H, W = cur[2]
         cu, al, info = kf_update_ref(ref, cu, al, uv, st, W, H, MARGIN, gap, self.keyframe_select)
         self._kf = [ref, cu, al]
+        if self.frame_pose is not None:
+            from .frame_pose import frame_pose_ref
+
+            f, cx, cy, b = self.camera
+            _, self._kf_pose = frame_pose_ref(np.column_stack([ref, self._kf_xr]), cu, al, f, cx, cy, b, self.frame_pose,
+                                              start=self._kf_pose)
+            info["pose"] = self._kf_pose
         return info
 
     def kf_guess(self) -> np.ndarray:
@@ -904,20 +935,36 @@ class GPUBackend(Backend):
             self._raw[t] = self._raw.pop(key)
 
     # ---- keyframe selection on the front-end context.  Device block "kf" of n seeded features:
-    # ref_uv (8n) | cur_uv (8n) | new_uv (8n) | alive (n) | status (n), the info block at the next 16-byte boundary
+    # ref_uv (8n) | cur_uv (8n) | new_uv (8n) | alive (n) | status (n), the info block at the next 16-byte boundary.
+    # With the frame pose on: ref_uv | cur_uv | new_uv | ref_xr (4n) | alive | status, and the 128-byte pose block
+    # directly behind the 32-byte info block
     _kf_n = 0
     _kf_ref = None
 
     def _kf_block(self):
         n = self._kf_n
+        if self.frame_pose is not None:
+            o_info = 16 * ((30 * n + 15) // 16)
+            return self._dbuf("kf", o_info + 160), o_info
         o_info = 16 * ((26 * n + 15) // 16)
         return self._dbuf("kf", o_info + 32), o_info
 
-    def kf_seed(self, pts):
+    def kf_seed(self, pts, xr=None):
         pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
         n = self._kf_n = len(pts)
         self._kf_ref = pts.copy()
-        d, _ = self._kf_block()
+        d, o_info = self._kf_block()
+        if self.frame_pose is not None:
+            # one copy of the whole block: x_r rides beside the positions, the pose block behind the info block
+            # is zeroed (valid = 0: the first frame after the keyframe starts at identity)
+            hp = self._hbuf("kf_in", o_info + 160)
+            self._view(hp, np.uint8, o_info + 160)[:] = 0
+            self._view(hp, np.float32, 2 * n)[:] = pts.ravel()
+            self._view(hp, np.float32, 2 * n, 8 * n)[:] = pts.ravel()
+            self._view(hp, np.float32, n, 24 * n)[:] = np.ascontiguousarray(xr, np.float32).reshape(-1)
+            self._view(hp, np.uint8, n, 28 * n)[:] = 1
+            self.tctx.copy_async(d, hp, o_info + 160)
+            return
         if n == 0:
             return
         hp = self._hbuf("kf_in", 25 * n)
@@ -937,24 +984,42 @@ class GPUBackend(Backend):
         H, W = cur[2]
         c = self.tctx
         d, o_info = self._kf_block()
+        fp = self.frame_pose
+        o_al = (28 if fp is not None else 24) * n  # alive, then status
         V = ctypes.c_void_p
         if n:
             kp = klt_params()
             if self.klt_fb_max > 0.0:
                 c.check(c.lib.me_klt_track_fb(c.h, ME_DEVICE, V(prev[0]), V(cur[0]), W, H, W, V(d + 8 * n), V(d + 16 * n),
-                                              V(d + 25 * n), None, n, ctypes.byref(kp), float(self.klt_fb_max)),
+                                              V(d + o_al + n), None, n, ctypes.byref(kp), float(self.klt_fb_max)),
                         "me_klt_track_fb")
             else:
                 c.check(c.lib.me_klt_track(c.h, ME_DEVICE, V(prev[0]), V(cur[0]), W, H, W, V(d + 8 * n), V(d + 16 * n),
-                                           V(d + 25 * n), n, ctypes.byref(kp)), "me_klt_track")
-            kf_update_device(c, self.keyframe_select, d, d + 8 * n, d + 24 * n, d + 16 * n, d + 25 * n, n, W, H, MARGIN,
+                                           V(d + o_al + n), n, ctypes.byref(kp)), "me_klt_track")
+            kf_update_device(c, self.keyframe_select, d, d + 8 * n, d + o_al, d + 16 * n, d + o_al + n, n, W, H, MARGIN,
                              gap, d + o_info)
         else:
             kf_update_device(c, self.keyframe_select, 0, 0, 0, 0, 0, 0, W, H, MARGIN, gap, d + o_info)
-        ho = self._hbuf("kf_out", 32)
-        c.copy_async(ho, d + o_info, 32)
+        nb = 32
+        if fp is not None:  # right behind the update, from the previous frame's pose (start == info)
+            from .frame_pose import frame_pose_device
+            from .frame_pose import parse_info as parse_pose
+
+            f, cx, cy, b = self.camera
+            d_pose = d + o_info + 32
+            if n:
+                frame_pose_device(c, fp, d, d + 24 * n, d + 8 * n, d + o_al, n, f, cx, cy, b, d_pose, d_pose)
+            else:
+                frame_pose_device(c, fp, 0, 0, 0, 0, 0, f, cx, cy, b, d_pose, d_pose)
+            nb = 160
+        ho = self._hbuf("kf_out", nb)
+        c.copy_async(ho, d + o_info, nb)
         c.synchronize()
-        return parse_info(self._view(ho, np.uint8, 32).copy())
+        raw = self._view(ho, np.uint8, nb).copy()
+        info = parse_info(raw[:32])
+        if fp is not None:
+            info["pose"] = parse_pose(raw[32:])
+        return info
 
     def kf_guess(self):
         n = self._kf_n
@@ -962,11 +1027,12 @@ class GPUBackend(Backend):
             return np.zeros((0, 2), np.float32)
         c = self.tctx
         d, _ = self._kf_block()
-        ho = self._hbuf("kf_state", 17 * n)
-        c.copy_async(ho, d + 8 * n, 17 * n)  # cur_uv | new_uv | alive
+        nb = (21 if self.frame_pose is not None else 17) * n
+        ho = self._hbuf("kf_state", nb)
+        c.copy_async(ho, d + 8 * n, nb)  # cur_uv | new_uv | (ref_xr |) alive
         c.synchronize()
         cu = self._view(ho, np.float32, 2 * n).reshape(n, 2)
-        al = self._view(ho, np.uint8, n, 16 * n)
+        al = self._view(ho, np.uint8, n, nb - n)
         return np.where(al[:, None] != 0, cu, self._kf_ref)
 
     def close(self):
@@ -1547,10 +1613,13 @@ class WindowedStereoVO:
         self.be.tonemapper = cfg.tonemap
         self.be.motion_gate = cfg.motion_gate
         self.be.keyframe_select = cfg.keyframe_select
+        self.be.frame_pose = cfg.frame_pose
         # push(): frames pushed so far, frames since the last keyframe, the previous pushed frame's images and
         # their key (None: a keyframe's), the images a keyframe's process() call finds prepared
         self._n_pushed, self._kf_gap, self._kf_prev, self._kf_prev_key, self._prepared = 0, 0, None, None, None
-        self.kf_log = []  # per pushed frame: dict(frame, t (-1: no keyframe), gap, guided, n, m, rank, flags, med2)
+        # per pushed frame: dict(frame, t (-1: no keyframe), gap, guided, n, m, rank, flags, med2); with
+        # cfg.frame_pose every frame but the first also t_ref, pose_valid, n_usable, n_inliers, steps, R_rel, t_rel
+        self.kf_log = []
         if hasattr(backend, "reserve"):
             backend.reserve(cfg)
         self.K = np.asarray(S.intrinsics(cfg.width, cfg.height) if K is None else K, np.float64)
@@ -1864,6 +1933,10 @@ class WindowedStereoVO:
             info = self._wait(self.be.kf_track, self._kf_prev, imgs, self._kf_gap)
             rec.update(gap=self._kf_gap, n=info["n"], m=info["m"], rank=info["rank"], flags=info["flags"],
                        med2=info["med2"])
+            if "pose" in info:  # relative to the keyframe the state was seeded from: read only, nothing feeds on it
+                fp = info["pose"]
+                rec.update(t_ref=self.prev_t, pose_valid=fp["valid"], n_usable=fp["n_usable"], n_inliers=fp["n_inliers"],
+                           steps=fp["steps"], R_rel=np.array(fp["R"], np.float64), t_rel=np.array(fp["t"], np.float64))
             if self._kf_prev_key is not None:  # (the frame before this one was no keyframe: its images go)
                 self.be.release(self._kf_prev_key)
             if not info["keyframe"]:
@@ -1882,9 +1955,25 @@ class WindowedStereoVO:
         pid, puv = self.obs[t]
         aid = self.ids[act]
         pos = np.arange(len(pid)) if len(aid) == len(pid) and np.array_equal(aid, pid) else np.searchsorted(pid, aid)
-        self.be.kf_seed(np.ascontiguousarray(puv[pos, :2]))
+        if cfg.frame_pose is not None:
+            self.be.kf_seed(np.ascontiguousarray(puv[pos, :2]), np.ascontiguousarray(puv[pos, 2]))
+        else:
+            self.be.kf_seed(np.ascontiguousarray(puv[pos, :2]))
         self._kf_prev, self._kf_prev_key, self._kf_gap = imgs, None, 0
         return t
+
+    def frame_pose(self, frame: int):
+        """(R, t, valid) of pushed frame `frame`, world -> camera
+        (PipelineConfig.frame_pose): the frame's motion from its keyframe on
+        top of the keyframe pose the loop holds now (the BA-refined one after
+        finish()).  Frame 0 is the first pose, valid = 1."""
+        if self.cfg.frame_pose is None:
+            raise ValueError("WindowedStereoVO.frame_pose: needs PipelineConfig.frame_pose")
+        rec = self.kf_log[frame]
+        if "t_ref" not in rec:
+            p = self.poses[rec["t"]]
+            return aa_to_R(p[3:]), np.array(p[:3], np.float64), 1
+        return compose_frame_pose(self.poses[rec["t_ref"]], rec["R_rel"], rec["t_rel"]) + (int(rec["pose_valid"]),)
 
     def finish(self):
         """Complete the last queued keyframe (its pops, scale LM, BA)."""
@@ -2162,6 +2251,9 @@ class NativeStereoVO:
                 kc = cfg.keyframe_select.to_c()
                 self._check(self.lib.me_vo_loop_set_keyframe_select(self.h, ctypes.byref(kc)),
                             "me_vo_loop_set_keyframe_select")
+            if cfg.frame_pose is not None:  # (after the keyframe switch it needs)
+                fc = cfg.frame_pose.to_c()
+                self._check(self.lib.me_vo_loop_set_frame_pose(self.h, ctypes.byref(fc)), "me_vo_loop_set_frame_pose")
             if cfg.rectify is not None:  # the loop builds the two maps itself, on its front context
                 cl, cr = cfg.rectify.left.to_c(), cfg.rectify.right.to_c()
                 self._check(self.lib.me_vo_loop_set_rectify(self.h, ctypes.byref(cl), ctypes.byref(cr),
@@ -2336,6 +2428,32 @@ class NativeStereoVO:
         return [FrameResult(r.t, r.n_tracked, r.n_new, r.n_active, r.n_window_pts, r.n_window_obs, r.scale,
                             r.scale_stop, r.scale_iters, r.ba_iters, r.ba_cost, np.array(r.pose[:], np.float64))
                 for r in arr[:n.value]]
+
+    @property
+    def frame_pose_log(self):
+        """me_vo_loop_frame_poses: per pushed frame after the first, the fields
+        WindowedStereoVO.kf_log gains with PipelineConfig.frame_pose."""
+        import ctypes
+
+        from ._lib import VoFramePoseC
+
+        n = ctypes.c_int()
+        self._check(self.lib.me_vo_loop_frame_poses(self.h, None, 0, ctypes.byref(n)), "frame_poses")
+        arr = (VoFramePoseC * max(n.value, 1))()
+        self._check(self.lib.me_vo_loop_frame_poses(self.h, arr, n.value, ctypes.byref(n)), "frame_poses")
+        return [dict(frame=r.frame, t=r.t, t_ref=r.t_ref, gap=r.gap, pose_valid=r.valid, n_usable=r.n_usable,
+                     n_inliers=r.n_inliers, steps=r.steps, R_rel=np.array(r.R[:], np.float64).reshape(3, 3),
+                     t_rel=np.array(r.t_rel[:], np.float64)) for r in arr[:n.value]]
+
+    def frame_pose(self, frame: int):
+        """WindowedStereoVO.frame_pose: (R, t, valid) of pushed frame `frame`, world -> camera."""
+        if self.cfg.frame_pose is None:
+            raise ValueError("NativeStereoVO.frame_pose: needs PipelineConfig.frame_pose")
+        poses = self.poses
+        if frame == 0:
+            return aa_to_R(poses[0][3:]), np.array(poses[0][:3], np.float64), 1
+        rec = self.frame_pose_log[frame - 1]
+        return compose_frame_pose(poses[rec["t_ref"]], rec["R_rel"], rec["t_rel"]) + (int(rec["pose_valid"]),)
 
     def event_records(self) -> np.ndarray:
         """The WBA_Point event log as a numpy record array (kind 0 new, 1 add, 2 pop, 3 del)."""
