@@ -506,8 +506,9 @@ int me_vo_loop_set_rectify(me_vo_loop* v, const struct me_camera_model* left, co
    front-end stream ahead of the KLT -- after the remaps when the loop also
    rectifies -- and every later stage (KLT, corner detector, both matchers,
    scale LM) reads the equalised pair.  Caller-owned device images are never
-   written: they are equalised into loop-owned buffers (three pairs, the rule
-   of the loop's other image slots); uploaded host images and rectified pairs
+   written: they are equalised into a loop-owned pair (the loop's pool of at
+   most four pairs: a frame takes one that neither the previous pushed frame
+   nor the last two keyframes hold); uploaded, tone-mapped and rectified pairs
    are equalised in place.  The lifetime rule of caller images is unchanged.
    NULL switches it off (the default: the loop runs exactly the calls it runs
    without this setter).  Bad parameters (me_clahe's rules, against the loop's
@@ -545,9 +546,10 @@ int me_vo_loop_set_motion_gate(me_vo_loop* v, const struct me_motion_gate_params
 /* Keyframe t as 16-bit images: width x height of the loop (stride = width), or
    the two camera models' raw sizes when the loop rectifies.  ME_ERR_STATE
    unless me_vo_loop_set_tonemap is on.  The two tone maps (me_tonemap16, each
-   with its camera's state) are queued on the front-end stream first, into
-   loop-owned 8-bit buffers (three pairs, slot t mod 3, the rule of the loop's
-   other image slots); caller images are never written.  Then the remaps, the
+   with its camera's state) are queued on the front-end stream first, into a
+   loop-owned 8-bit pair (the keyframe's pair of the loop's pool, or with a
+   rectifier one raw-size buffer reused in stream order, which the remaps
+   read); caller images are never written.  Then the remaps, the
    CLAHE and every later stage run as in me_vo_loop_process on that 8-bit pair.
    Nothing is read back: a keyframe keeps its one submission and round trip.
    mem and the lifetime rule of caller device images are me_vo_loop_process's.

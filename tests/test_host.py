@@ -166,6 +166,22 @@ def test_roster_protocol_host_threads():
     assert "roster_test: ok" in p.stdout
 
 
+# --------------------------------------------------- the VO loop's block layouts and pair pool (csrc/vo_blocks.hpp)
+def test_vo_loop_block_layouts_and_pool_rule():
+    """The byte layouts of the native loop's packed device blocks (res, new,
+    klt_in, kf with and without the frame pose) against the arithmetic the
+    loop used before they had names, for n in {0, 1, 2, 15, 16, 17, 2000};
+    the new-feature block's host decode; and the pair pool's slot rule over
+    10 000 frames: always < 4, never a slot that the previous pushed frame or
+    either of the last two keyframes holds, and t % 3 when every frame is a
+    keyframe.  Run by tests/cpp/vo_blocks_test."""
+    exe = os.path.join(ROOT, "tests", "cpp", "vo_blocks_test")
+    assert os.path.exists(exe), "build() compiles tests/cpp/vo_blocks_test"
+    p = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stderr
+    assert "vo_blocks_test: ok" in p.stdout
+
+
 def test_scale_lm_launch_form_selection():
     """me_scale_persistent (host only): the one persistent scale-LM launch
     while its nb x 2 workgroups take at most half of the co-resident capacity,

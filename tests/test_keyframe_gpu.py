@@ -191,6 +191,95 @@ def test_native_setter_and_entry_rules(ctx):
         PL.NativeStereoVO(C.loop_config(), ctx, K, p0, v, overlap=False).push(fr[0].left, fr[0].right)
 
 
+# ------------------------------------------------------------------ push() behind the rectifier and CLAHE
+PUSH_SELECT = KeyframeSelect(min_parallax=0.0, min_tracked_pct=0, max_gap=3)
+_CHAIN = {}
+
+
+def chain_config(rectify):
+    """The stream's loop with CLAHE and the gap rule, and the cropping rectifier of padded frames when asked for."""
+    import rectify_cases as RC
+    from uasl_motion_estimation_amd.equalise import Clahe
+
+    kw = dict(rectify=RC.padded_rectifier(C.SW, C.SH, C.stream()[1])) if rectify else {}
+    return C.loop_config(PUSH_SELECT, equalise=Clahe(), **kw)
+
+
+def chain_frames(rectify):
+    """The stream as 16-level frames whose level drifts (equalise_cases.low_frame), padded for the rectifier."""
+    import equalise_cases as EC
+    import rectify_cases as RC
+
+    out = [(EC.low_frame(f.left, i), EC.low_frame(f.right, i)) for i, f in enumerate(C.stream()[0])]
+    return [(RC.pad_frame(L), RC.pad_frame(R)) for L, R in out] if rectify else out
+
+
+def chain_oracle(rectify):
+    """(loop, keyframe index per frame) of push() on the oracle backend with the same switches, computed once.
+    Guarded: the run has guided keyframes that track, so a loop that equals it has run the whole chain."""
+    from pipeline_oracle import OracleBackend
+
+    if rectify not in _CHAIN:
+        _, K, p0, v = C.stream()
+        vo = PL.WindowedStereoVO(chain_config(rectify), OracleBackend(), K, p0, v, log_events=True)
+        kts = [vo.push(L, R) for L, R in chain_frames(rectify)]
+        vo.finish()
+        assert sum(bool(r["guided"]) for r in vo.kf_log) >= 4
+        assert len(vo.results) >= 5 and all(r.n_tracked >= 20 for r in vo.results[1:])
+        _CHAIN[rectify] = (vo, kts)
+    return _CHAIN[rectify]
+
+
+def check_chain(g, kts, rectify):
+    o, okts = chain_oracle(rectify)
+    print(kts, [r.n_tracked for r in g.results], len(g.events))
+    assert kts == okts and g.events == o.events
+    assert len(g.results) == len(o.results)
+    for a, b in zip(g.results, o.results):
+        np.testing.assert_allclose(a.pose, b.pose, rtol=0, atol=1e-6)  # (the loops' bar, as above)
+
+
+def test_oracle_push_chain_is_the_same_with_and_without_the_rectifier(oracle):
+    (a, ka), (b, kb) = chain_oracle(False), chain_oracle(True)
+    assert ka == kb and a.events == b.events
+
+
+@pytest.mark.parametrize("rectify,tensors", [(True, False), (True, True), (False, True)],
+                         ids=["rectify-equalise-host", "rectify-equalise-tensors", "equalise-tensors"])
+def test_native_push_behind_the_front_end_chain(ctx, oracle, rectify, tensors):
+    """me_vo_loop_push with the rectifier and CLAHE on, from host arrays and from the caller's device tensors
+    (remap into the loop's pair, CLAHE in place; without the rectifier CLAHE out of place from the caller's
+    images): the oracle-backend run's keyframes, events and poses, and the caller's tensors come back unchanged."""
+    import torch
+
+    _, K, p0, v = C.stream()
+    frames = chain_frames(rectify)
+    fed = [(torch.from_numpy(L).cuda(), torch.from_numpy(R).cuda()) for L, R in frames] if tensors else frames
+    g = PL.NativeStereoVO(chain_config(rectify), ctx, K, p0, v, log_events=True)
+    try:
+        kts = [g.push(L, R) for L, R in fed]
+        g.finish()
+        check_chain(g, kts, rectify)
+    finally:
+        g.close()
+    if tensors:
+        torch.cuda.synchronize()
+        for (dL, dR), (L, R) in zip(fed, frames):
+            assert np.array_equal(dL.cpu().numpy(), L) and np.array_equal(dR.cpu().numpy(), R)
+
+
+def test_python_gpu_push_behind_the_front_end_chain(ctx, oracle):
+    _, K, p0, v = C.stream()
+    be = PL.GPUBackend(ctx)
+    try:
+        g = PL.WindowedStereoVO(chain_config(True), be, K, p0, v, log_events=True, overlap=True)
+        kts = [g.push(L, R) for L, R in chain_frames(True)]
+        g.finish()
+        check_chain(g, kts, True)
+    finally:
+        be.close()
+
+
 def test_cpp_caller_prints_the_recorded_keyframes(ctx, tmp_path):
     want_kts, _ = C.golden()
     exe = C.build_cli(tmp_path)

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "me_internal.hpp"
+#include "vo_blocks.hpp"
 
 namespace {
 
@@ -207,29 +208,21 @@ struct me_vo_loop {
   me_vo_loop_config cfg{};
   double match_lr = 0.0;  // > 0: every matcher call takes its _lr form with this bound (me_vo_loop_set_match_lr)
   std::string err;
-  // the rigid-motion gate (me_vo_loop_set_motion_gate, me_hip.h A12h): queued behind the tracked features' matcher;
-  // gate_xr: byte offset of the previous keyframe's x_r in the "klt_in" device buffer of the keyframe in flight
+  // the rigid-motion gate (me_vo_loop_set_motion_gate, me_hip.h A12h): queued behind the tracked features' matcher
   bool gate = false;
   me_motion_gate_params gate_params{};
-  size_t gate_xr = 0;
   bool klt_predict = false;  // the tracker starts at each landmark's predicted pixel (me_vo_loop_set_klt_predict)
   // ---- keyframe selection (me_vo_loop_set_keyframe_select / me_vo_loop_push, me_hip.h A12i).  Device block
-  // "kf" of the kf_n features seeded at the last keyframe: ref_uv (8n) | cur_uv (8n) | new_uv (8n) | alive (n) |
-  // status (n), the info block at the next 16-byte boundary.  Pushed frames are prepared into four loop-owned
-  // pairs: a new frame takes a slot that neither the previous pushed frame nor the last two keyframes hold.
+  // "kf" of the kf_n features seeded at the last keyframe: me_vo::Kf (vo_blocks.hpp)
   bool kf_on = false;
   me_kf_params kf_params{};
   int kf_n = 0, kf_gap = 0;  // seeded features; frames pushed since the last keyframe
   long n_pushed = 0;
   std::vector<float> kf_ref;  // the seeded features' positions in the last keyframe
-  void* push_slot[4] = {nullptr, nullptr, nullptr, nullptr};
-  // the frame pose (me_vo_loop_set_frame_pose, me_hip.h A12j): the block becomes ref_uv | cur_uv | new_uv |
-  // ref_xr (4n) | alive | status, and the 128-byte pose block sits directly behind the 32-byte info block
+  // the frame pose (me_vo_loop_set_frame_pose, me_hip.h A12j): me_vo::Kf with the pose block
   bool fpose = false;
   me_frame_pose_params fpose_params{};
   std::vector<me_vo_frame_pose> fposes;  // per pushed frame after the first
-  int push_prev = -1, push_kf[2] = {-1, -1};  // slots of the previous pushed frame (-1: a keyframe), the last two keyframes
-  const std::vector<float>* kf_guess = nullptr;  // set around process(): the tracker's guess, ahead of klt_predict's
   double f = 0, cx = 0, cy = 0;
   int nx = 1, ny = 1;
   double cw = 1, ch = 1;
@@ -253,32 +246,29 @@ struct me_vo_loop {
     const uint8_t* R = nullptr;
   };
   std::map<int, Imgs> imgs;
-  Buf img_slot[3];
-  Imgs push_imgs;  // me_vo_loop_push: the previous pushed frame's prepared pair (while push_prev >= 0)
-  // ---- rectification (me_vo_loop_set_rectify): the two maps, the raw sizes, one upload buffer for host
-  // images and three rectified pairs (a keyframe's pair is read during its call and the next one, by the
-  // scale LM of the call after as well: the rule of img_slot)
+  // the pair pool (me_vo::pool_pick): 8-bit pairs of width x height x 2 bytes that the image chain's last stage
+  // writes, allocated on first use; the slots of the previous pushed frame (-1: a keyframe) and the last two
+  // keyframes, and the previous pushed frame's pair (while slot_prev >= 0)
+  void* pool[me_vo::kPoolSlots] = {nullptr, nullptr, nullptr, nullptr};
+  int slot_prev = -1, slot_kf[2] = {-1, -1};
+  Imgs push_imgs;
+  // the chain's intermediates, single buffers allocated on first use and reused in stream order: host images
+  // that a tone map or a remap reads are uploaded into stage_in, the tone map ahead of a remap writes stage_tm
+  void *stage_in = nullptr, *stage_tm = nullptr;
+  // ---- rectification (me_vo_loop_set_rectify): the two maps and the raw sizes
   bool rectify = false;
   int rect_border = 0;
   int raw_w[2] = {0, 0}, raw_h[2] = {0, 0};
   void* rect_map[2] = {nullptr, nullptr};
-  void* rect_raw = nullptr;
-  void* rect_slot[3] = {nullptr, nullptr, nullptr};
-  // ---- equalisation (me_vo_loop_set_equalise): the parameters and, for caller-owned device images only,
-  // three equalised pairs (allocated on first use; the rule of img_slot)
+  // ---- equalisation (me_vo_loop_set_equalise)
   bool equalise = false;
   me_clahe_params eq_params{};
-  void* eq_slot[3] = {nullptr, nullptr, nullptr};
-  // ---- 16-bit ingest (me_vo_loop_set_tonemap): the parameters, a state per camera, one upload buffer for host
-  // images and three 8-bit pairs (allocated on first use; the rule of img_slot).  depth: the entry point the
-  // loop's keyframes come through (0: none yet, 8, 16)
+  // ---- 16-bit ingest (me_vo_loop_set_tonemap): the parameters and a state per camera.  depth: the entry point
+  // the loop's keyframes come through (0: none yet, 8, 16)
   bool tonemap = false;
   me_tonemap_params tm_params{};
   me_tonemap_state* tm_state[2] = {nullptr, nullptr};
-  void* tm_raw = nullptr;
-  void* tm_slot[3] = {nullptr, nullptr, nullptr};
   int depth = 0;
-  bool own_device_pair = false;  // process16 only: the device pair handed to frame_images is the loop's (tm_slot)
   bool has_prev = false;
   int prev_t = -1;
   // ---- lagged state
@@ -477,14 +467,11 @@ struct me_vo_loop {
     me_synchronize(ctx);
     for (auto& w : wstore)
       if (w) me_free(ctx, w);
-    for (auto& b : img_slot)
-      if (b.p) me_free(tctx, b.p);
-    for (auto& p : push_slot) {
-      if (p) me_free(tctx, p);
-      p = nullptr;
+    for (void** p : {&pool[0], &pool[1], &pool[2], &pool[3], &stage_in, &stage_tm}) {
+      if (*p) me_free(tctx, *p);
+      *p = nullptr;
     }
     rectify_off();
-    equalise_off();
     tonemap_off();
     for (auto& kv : dev) me_free(tctx, kv.second.p);
     for (auto& kv : pin) me_host_free(tctx, kv.second.p);
@@ -547,12 +534,6 @@ struct me_vo_loop {
       if (p) me_free(tctx, p);
       p = nullptr;
     }
-    for (auto& p : rect_slot) {
-      if (p) me_free(tctx, p);
-      p = nullptr;
-    }
-    if (rect_raw) me_free(tctx, rect_raw);
-    rect_raw = nullptr;
     rectify = false;
   }
   // The maps of the two cameras, built once on the front context; the rectified model is the loop's own
@@ -567,75 +548,12 @@ struct me_vo_loop {
       raw_w[k] = cam[k]->width;
       raw_h[k] = cam[k]->height;
     }
-    for (auto& p : rect_slot) VL_TRY(me_malloc(tctx, &p, 2 * npx), "malloc");
-    VL_TRY(me_malloc(tctx, &rect_raw, (size_t)raw_w[0] * raw_h[0] + (size_t)raw_w[1] * raw_h[1]), "malloc");
     VL_TRY(me_synchronize(tctx), "me_vo_loop_set_rectify");
     rect_border = border;
     rectify = true;
     return ME_OK;
   }
-  // Raw pair -> rectified pair of keyframe t, two remaps queued on the front-end stream ahead of the KLT
-  int frame_images_rectified(int t, const uint8_t* L, const uint8_t* R, me_mem mem) {
-    const size_t nl = (size_t)raw_w[0] * raw_h[0], nr = (size_t)raw_w[1] * raw_h[1];
-    if (mem != ME_DEVICE) {
-      VL_TRY(me_memcpy_async(tctx, rect_raw, L, nl), "image upload");
-      VL_TRY(me_memcpy_async(tctx, (uint8_t*)rect_raw + nl, R, nr), "image upload");
-      L = (const uint8_t*)rect_raw;
-      R = L + nl;
-    }
-    const size_t npx = (size_t)cfg.width * cfg.height;
-    uint8_t* o = (uint8_t*)rect_slot[t % 3];
-    VL_TRY(me_remap_q5(tctx, ME_DEVICE, L, raw_w[0], raw_h[0], raw_w[0], (const int32_t*)rect_map[0], cfg.width,
-                       cfg.height, rect_border, o, cfg.width, nullptr),
-           "me_remap_q5");
-    VL_TRY(me_remap_q5(tctx, ME_DEVICE, R, raw_w[1], raw_h[1], raw_w[1], (const int32_t*)rect_map[1], cfg.width,
-                       cfg.height, rect_border, o + npx, cfg.width, nullptr),
-           "me_remap_q5");
-    Imgs im;
-    im.L = o;
-    im.R = o + npx;
-    if (equalise) {
-      const int rc = equalise_pair(t, im, true);
-      if (rc != ME_OK) return rc;
-    }
-    imgs[t] = im;
-    return ME_OK;
-  }
-
-  void equalise_off() {
-    for (auto& p : eq_slot) {
-      if (p) me_free(tctx, p);
-      p = nullptr;
-    }
-    equalise = false;
-  }
-  // Keyframe t's pair -> its equalised pair, two me_clahe queued on the front-end stream ahead of the KLT:
-  // in place where the loop owns the images, into eq_slot[t % 3] where they are the caller's
-  int equalise_pair(int t, Imgs& im, bool loop_owned) {
-    const size_t npx = (size_t)cfg.width * cfg.height;
-    uint8_t *oL = const_cast<uint8_t*>(im.L), *oR = const_cast<uint8_t*>(im.R);
-    if (!loop_owned) {
-      void*& p = eq_slot[t % 3];
-      if (p == nullptr) VL_TRY(me_malloc(tctx, &p, 2 * npx), "malloc");
-      oL = (uint8_t*)p;
-      oR = oL + npx;
-    }
-    VL_TRY(me_clahe(tctx, ME_DEVICE, im.L, cfg.width, cfg.height, cfg.width, &eq_params, oL, cfg.width, nullptr),
-           "me_clahe");
-    VL_TRY(me_clahe(tctx, ME_DEVICE, im.R, cfg.width, cfg.height, cfg.width, &eq_params, oR, cfg.width, nullptr),
-           "me_clahe");
-    im.L = oL;
-    im.R = oR;
-    return ME_OK;
-  }
-
   void tonemap_off() {
-    for (auto& p : tm_slot) {
-      if (p) me_free(tctx, p);
-      p = nullptr;
-    }
-    if (tm_raw) me_free(tctx, tm_raw);
-    tm_raw = nullptr;
     for (auto& st : tm_state) {
       if (st) me_tonemap_state_destroy(st);
       st = nullptr;
@@ -649,100 +567,104 @@ struct me_vo_loop {
     tonemap = true;
     return ME_OK;
   }
-  // Keyframe t's 16-bit pair -> its 8-bit pair in tm_slot[t % 3], two me_tonemap16 queued on the front-end
-  // stream ahead of everything else; sizes are the loop's, or the camera models' when it rectifies.  The
-  // 8-bit pair then enters frame_images as device images nobody else writes.
-  int tonemap_pair(int t, const uint16_t* L, const uint16_t* R, me_mem mem, const uint8_t** oL, const uint8_t** oR) {
+
+  // The image chain of every frame entry, queued on the front-end stream ahead of the tracker: bring to the
+  // device -> me_tonemap16 (depth 16) -> two me_remap_q5 -> two me_clahe, each stage only with its switch.  The
+  // last of the first three that runs writes pool[slot], earlier ones the intermediates; CLAHE then runs in place
+  // there, or out of place from the caller's device images, which are never written.  With no stage at all the
+  // caller's device pair is used as it is, unless the result must be the loop's (owned: me_vo_loop_push), then
+  // it is copied.  Sizes ahead of the remap are the camera models', the loop's otherwise.
+  int prepare(const void* L, const void* R, me_mem mem, int bits, bool owned, int slot, Imgs& im) {
+    const bool wide = bits == 16, host = mem != ME_DEVICE;
+    const uint8_t *sl = (const uint8_t*)L, *sr = (const uint8_t*)R;  // the pair so far
+    if (!(host || wide || rectify || equalise || owned)) {
+      im = Imgs{sl, sr};
+      return ME_OK;
+    }
+    const size_t npx = (size_t)cfg.width * cfg.height;
+    if (pool[slot] == nullptr) VL_TRY(me_malloc(tctx, &pool[slot], 2 * npx), "malloc");
+    uint8_t *oL = (uint8_t*)pool[slot], *oR = oL + npx;
     const int w[2] = {rectify ? raw_w[0] : cfg.width, rectify ? raw_w[1] : cfg.width};
     const int h[2] = {rectify ? raw_h[0] : cfg.height, rectify ? raw_h[1] : cfg.height};
-    const size_t nl = (size_t)w[0] * h[0], nr = (size_t)w[1] * h[1];
-    if (mem != ME_DEVICE) {
-      if (tm_raw == nullptr) VL_TRY(me_malloc(tctx, &tm_raw, 2 * (nl + nr) + 16), "malloc");
-      uint16_t* dl = (uint16_t*)tm_raw;
-      uint16_t* dr = (uint16_t*)((uint8_t*)tm_raw + ((2 * nl + 15) & ~(size_t)15));
-      VL_TRY(me_memcpy_async(tctx, dl, L, 2 * nl), "image upload");
-      VL_TRY(me_memcpy_async(tctx, dr, R, 2 * nr), "image upload");
-      L = dl;
-      R = dr;
-    }
-    void*& p = tm_slot[t % 3];
-    if (p == nullptr) VL_TRY(me_malloc(tctx, &p, nl + nr + 16), "malloc");
-    uint8_t* o = (uint8_t*)p;
-    uint8_t* o2 = o + ((nl + 15) & ~(size_t)15);
-    VL_TRY(me_tonemap16(tctx, ME_DEVICE, L, w[0], h[0], w[0], o, w[0], &tm_params, tm_state[0]), "me_tonemap16");
-    VL_TRY(me_tonemap16(tctx, ME_DEVICE, R, w[1], h[1], w[1], o2, w[1], &tm_params, tm_state[1]), "me_tonemap16");
-    *oL = o;
-    *oR = o2;
-    return ME_OK;
-  }
-
-  int frame_images(int t, const uint8_t* L, const uint8_t* R, me_mem mem) {
-    if (imgs.count(t)) return ME_OK;
-    if (rectify) return frame_images_rectified(t, L, R, mem);
-    Imgs im;
-    if (mem == ME_DEVICE) {
-      im.L = L;
-      im.R = R;
-    } else {
-      const size_t nb = (size_t)cfg.width * cfg.height;
-      Buf& b = img_slot[t % 3];
-      if (b.p == nullptr) {
-        VL_TRY(me_malloc(tctx, &b.p, 2 * nb), "malloc");
-        b.n = 2 * nb;
+    const size_t nl = (size_t)w[0] * h[0], nr = (size_t)w[1] * h[1], px = wide ? 2 : 1;
+    if (host || !(wide || rectify || equalise)) {
+      uint8_t *dl = oL, *dr = oR;
+      if (wide || rectify) {
+        if (stage_in == nullptr) VL_TRY(me_malloc(tctx, &stage_in, px * (nl + nr) + 16), "malloc");
+        dl = (uint8_t*)stage_in;
+        dr = dl + (wide ? me_vo::align16(2 * nl) : nl);
       }
-      VL_TRY(me_memcpy_async(tctx, b.p, L, nb), "image upload");
-      VL_TRY(me_memcpy_async(tctx, (uint8_t*)b.p + nb, R, nb), "image upload");
-      im.L = (const uint8_t*)b.p;
-      im.R = (const uint8_t*)b.p + nb;
+      VL_TRY(me_memcpy_async(tctx, dl, sl, px * nl), "image upload");
+      VL_TRY(me_memcpy_async(tctx, dr, sr, px * nr), "image upload");
+      sl = dl;
+      sr = dr;
     }
-    if (equalise) {
-      // (in place where the pair is the loop's: an uploaded copy, or process16's tone-mapped pair)
-      const int rc = equalise_pair(t, im, mem != ME_DEVICE || own_device_pair);
-      if (rc != ME_OK) return rc;
+    if (wide) {
+      uint8_t *dl = oL, *dr = oR;
+      if (rectify) {
+        if (stage_tm == nullptr) VL_TRY(me_malloc(tctx, &stage_tm, nl + nr + 16), "malloc");
+        dl = (uint8_t*)stage_tm;
+        dr = dl + me_vo::align16(nl);
+      }
+      VL_TRY(me_tonemap16(tctx, ME_DEVICE, (const uint16_t*)sl, w[0], h[0], w[0], dl, w[0], &tm_params, tm_state[0]),
+             "me_tonemap16");
+      VL_TRY(me_tonemap16(tctx, ME_DEVICE, (const uint16_t*)sr, w[1], h[1], w[1], dr, w[1], &tm_params, tm_state[1]),
+             "me_tonemap16");
+      sl = dl;
+      sr = dr;
     }
-    imgs[t] = im;
+    if (rectify) {
+      VL_TRY(me_remap_q5(tctx, ME_DEVICE, sl, w[0], h[0], w[0], (const int32_t*)rect_map[0], cfg.width, cfg.height,
+                         rect_border, oL, cfg.width, nullptr),
+             "me_remap_q5");
+      VL_TRY(me_remap_q5(tctx, ME_DEVICE, sr, w[1], h[1], w[1], (const int32_t*)rect_map[1], cfg.width, cfg.height,
+                         rect_border, oR, cfg.width, nullptr),
+             "me_remap_q5");
+      sl = oL;
+      sr = oR;
+    }
+    if (equalise) {  // (sl == oL: in place)
+      VL_TRY(me_clahe(tctx, ME_DEVICE, sl, cfg.width, cfg.height, cfg.width, &eq_params, oL, cfg.width, nullptr), "me_clahe");
+      VL_TRY(me_clahe(tctx, ME_DEVICE, sr, cfg.width, cfg.height, cfg.width, &eq_params, oR, cfg.width, nullptr), "me_clahe");
+    }
+    im = Imgs{oL, oR};
     return ME_OK;
   }
 
   // ---- front end
   // guess (klt_predict): the features' predicted pixels, uploaded behind them in the same copy; prev_xr (the
   // rigid-motion gate): the previous keyframe's x_r, behind both
-  int klt_submit(const Imgs& prev, const Imgs& cur, const std::vector<float>& pts, const std::vector<float>* guess,
-                 const std::vector<float>* prev_xr) {
-    const int n = (int)pts.size() / 2;
-    gate_xr = (guess ? 16 : 8) * (size_t)n;
-    const size_t in_bytes = gate_xr + (prev_xr ? 4 : 0) * (size_t)n;
+  int klt_submit(const Imgs& prev, const Imgs& cur, const me_vo::KltIn& in, const std::vector<float>& pts,
+                 const std::vector<float>* guess, const std::vector<float>* prev_xr) {
+    const me_vo::Res res{in.n};
     void *hp, *d_in, *dres;
-    VL_TRY(hbuf("klt_in", in_bytes, &hp), "klt");
-    std::memcpy(hp, pts.data(), 8 * (size_t)n);
-    if (guess) std::memcpy((char*)hp + 8 * (size_t)n, guess->data(), 8 * (size_t)n);
-    if (prev_xr) std::memcpy((char*)hp + gate_xr, prev_xr->data(), 4 * (size_t)n);
-    VL_TRY(dbuf("klt_in", in_bytes, &d_in), "klt");
-    VL_TRY(dbuf("res", 14 * (size_t)n, &dres), "klt");
-    VL_TRY(me_memcpy_async(tctx, d_in, hp, in_bytes), "klt H2D");
+    VL_TRY(hbuf("klt_in", in.size(), &hp), "klt");
+    std::memcpy(in.pts(hp), pts.data(), 8 * in.n);
+    if (guess) std::memcpy(in.guess(hp), guess->data(), 8 * in.n);
+    if (prev_xr) std::memcpy(in.xr(hp), prev_xr->data(), 4 * in.n);
+    VL_TRY(dbuf("klt_in", in.size(), &d_in), "klt");
+    VL_TRY(dbuf("res", res.size(), &dres), "klt");
+    VL_TRY(me_memcpy_async(tctx, d_in, hp, in.size()), "klt H2D");
+    return track(prev, cur, in.pts(d_in), in.guess(d_in), res.uv(dres), res.status(dres), (int)in.n);
+  }
+  // The loop's tracker call: the guided tracker when there is a guess, and with cfg.klt_fb_max > 0 the
+  // forward-backward form, whose combined status is the byte the matcher gates on
+  int track(const Imgs& prev, const Imgs& cur, const float* pts, const float* guess, float* out, uint8_t* status, int n) {
     me_klt_params kp;
     me_klt_default_params(&kp);
-    if (guess) {
-      const float* d_guess = (const float*)d_in + 2 * (size_t)n;
-      if (cfg.klt_fb_max > 0.0)
-        VL_TRY(me_klt_track_guided_fb(tctx, ME_DEVICE, prev.L, cur.L, cfg.width, cfg.height, cfg.width,
-                                      (const float*)d_in, d_guess, (float*)dres, (uint8_t*)dres + 12 * (size_t)n,
-                                      nullptr, n, &kp, cfg.klt_fb_max),
-               "me_klt_track_guided_fb");
-      else
-        VL_TRY(me_klt_track_guided(tctx, ME_DEVICE, prev.L, cur.L, cfg.width, cfg.height, cfg.width,
-                                   (const float*)d_in, d_guess, (float*)dres, (uint8_t*)dres + 12 * (size_t)n, n, &kp),
-               "me_klt_track_guided");
-      return ME_OK;
-    }
-    if (cfg.klt_fb_max > 0.0)  // the forward-backward check: its combined status is the byte the matcher gates on
-      VL_TRY(me_klt_track_fb(tctx, ME_DEVICE, prev.L, cur.L, cfg.width, cfg.height, cfg.width, (const float*)d_in,
-                             (float*)dres, (uint8_t*)dres + 12 * (size_t)n, nullptr, n, &kp, cfg.klt_fb_max),
+    const int w = cfg.width, h = cfg.height;
+    const double fb = cfg.klt_fb_max;
+    if (guess && fb > 0.0)
+      VL_TRY(me_klt_track_guided_fb(tctx, ME_DEVICE, prev.L, cur.L, w, h, w, pts, guess, out, status, nullptr, n, &kp, fb),
+             "me_klt_track_guided_fb");
+    else if (guess)
+      VL_TRY(me_klt_track_guided(tctx, ME_DEVICE, prev.L, cur.L, w, h, w, pts, guess, out, status, n, &kp),
+             "me_klt_track_guided");
+    else if (fb > 0.0)
+      VL_TRY(me_klt_track_fb(tctx, ME_DEVICE, prev.L, cur.L, w, h, w, pts, out, status, nullptr, n, &kp, fb),
              "me_klt_track_fb");
     else
-      VL_TRY(me_klt_track(tctx, ME_DEVICE, prev.L, cur.L, cfg.width, cfg.height, cfg.width, (const float*)d_in,
-                          (float*)dres, (uint8_t*)dres + 12 * (size_t)n, n, &kp),
-             "me_klt_track");
+      VL_TRY(me_klt_track(tctx, ME_DEVICE, prev.L, cur.L, w, h, w, pts, out, status, n, &kp), "me_klt_track");
     return ME_OK;
   }
   // The loop's matcher calls: the plain entry points, or their left-right forms (me_hip.h A2b) when match_lr > 0
@@ -763,94 +685,78 @@ struct me_vo_loop {
     return me_mi_epipolar_match_count(tctx, im.L, im.R, cfg.width, cfg.height, cfg.width, uv, lo, n_dev, n_max, nd,
                                       kPatch, cfg.d_max, 1, kRatio, (float)kMargin, xr, ok);
   }
-  // GPUBackend.klt_match_new: tracked features' matcher, the cells they leave
-  // empty, the new features' matcher -- one submission, one round trip
-  int klt_match_new(int n, const Imgs& im, const std::vector<int32_t>& lo, const std::vector<uint8_t>& dvalid, int t,
-                    int nd, int nd_new, std::vector<float>& uv, std::vector<uint8_t>& st, std::vector<float>& xr,
-                    std::vector<uint8_t>& ok, std::vector<float>& nuv, std::vector<float>& nxr,
-                    std::vector<uint8_t>& nok) {
-    void *hp, *dl, *dres, *dn, *ho;
-    VL_TRY(hbuf("lo", 5 * (size_t)n, &hp), "match");
-    std::memcpy(hp, lo.data(), 4 * (size_t)n);
-    std::memcpy((uint8_t*)hp + 4 * (size_t)n, dvalid.data(), n);
-    VL_TRY(dbuf("lo", 5 * (size_t)n, &dl), "match");
-    VL_TRY(me_memcpy_async(tctx, dl, hp, 5 * (size_t)n), "match H2D");
-    VL_TRY(dbuf("res", 14 * (size_t)n, &dres), "match");
-    uint8_t* r8 = (uint8_t*)dres;
-    VL_TRY(epi_match(im, (const float*)dres, (const int32_t*)dl, (const uint8_t*)dl + 4 * (size_t)n,
-                     r8 + 12 * (size_t)n, n, nd, 0, (float*)(r8 + 8 * (size_t)n), r8 + 13 * (size_t)n),
-           "me_mi_epipolar_match");
-    if (gate) {  // in place on the ok byte the detector below and the host's good mask read
-      const uint8_t* d_in = (const uint8_t*)dev["klt_in"].p;
-      VL_TRY(me_motion_gate(tctx, (const float*)d_in, (const float*)(d_in + gate_xr), (const float*)dres,
-                            (const float*)(r8 + 8 * (size_t)n), r8 + 12 * (size_t)n, r8 + 13 * (size_t)n, n, f, cx, cy,
-                            cfg.baseline, cfg.width, cfg.height, (float)kMargin, t, &gate_params, r8 + 13 * (size_t)n,
-                            nullptr, nullptr),
-             "me_motion_gate");
-    }
-    const int m = std::max(cfg.n_feats, 1);
-    VL_TRY(dbuf("new", 16 + 17 * (size_t)m, &dn), "match");
-    uint8_t* n8 = (uint8_t*)dn;
+  // The new features of a keyframe, queued on the front end into block "new": the corner detector or the
+  // grid's empty cells, given the n tracked features in block "res" (n = 0: none), then their matcher
+  int new_features(const Imgs& im, void* dres, int n, int t, int nd_new, const me_vo::NewFeats& nf, void* dn) {
+    const me_vo::Res res{(size_t)n};
+    const float* uv = n ? res.uv(dres) : nullptr;
+    const uint8_t *st = n ? res.status(dres) : nullptr, *ok = n ? res.ok(dres) : nullptr;
     if (cfg.detector == 1) {
-      VL_TRY(new_corners(im, (const float*)dres, r8 + 12 * (size_t)n, r8 + 13 * (size_t)n, n, n8), "me_vo_new_corners");
+      const me_corner_params cp{cfg.corner_win, cfg.corner_min_eig};
+      VL_TRY(me_vo_new_corners(tctx, im.L, cfg.width, cfg.height, cfg.width, uv, st, ok, n, (float)kMargin, nx, ny, cw,
+                               ch, cfg.n_feats, cfg.d_min, &cp, nf.uv(dn), nf.lo(dn), nf.count(dn)),
+             "me_vo_new_corners");
     } else {
-      VL_TRY(me_vo_new_cells(tctx, (const float*)dres, r8 + 12 * (size_t)n, r8 + 13 * (size_t)n, n, cfg.width,
-                             cfg.height, (float)kMargin, nx, ny, cw, ch, cfg.n_feats, t, cfg.d_min,
-                             (float*)(n8 + 16), (int32_t*)(n8 + 16 + 12 * (size_t)m), (int32_t*)n8),
+      VL_TRY(me_vo_new_cells(tctx, uv, st, ok, n, cfg.width, cfg.height, (float)kMargin, nx, ny, cw, ch, cfg.n_feats, t,
+                             cfg.d_min, nf.uv(dn), nf.lo(dn), nf.count(dn)),
              "me_vo_new_cells");
     }
-    VL_TRY(epi_match_count(im, (const float*)(n8 + 16), (const int32_t*)(n8 + 16 + 12 * (size_t)m),
-                           (const int32_t*)n8, m, nd_new, (float*)(n8 + 16 + 8 * (size_t)m), n8 + 16 + 16 * (size_t)m),
+    VL_TRY(epi_match_count(im, nf.uv(dn), nf.lo(dn), nf.count(dn), (int)nf.m, nd_new, nf.xr(dn), nf.ok(dn)),
            "me_mi_epipolar_match_count");
-    const size_t o = 16 * ((14 * (size_t)n + 15) / 16);
-    VL_TRY(hbuf("out", o + 16 + 17 * (size_t)m, &ho), "match");
-    VL_TRY(me_memcpy_async(tctx, ho, dres, 14 * (size_t)n), "match D2H");
-    VL_TRY(me_memcpy_async(tctx, (uint8_t*)ho + o, dn, 16 + 17 * (size_t)m), "match D2H");
-    VL_TRY(timed_wait(0, [&] { return me_synchronize(tctx); }), "klt_match_new");
-    const uint8_t* h8 = (const uint8_t*)ho;
-    uv.assign((const float*)h8, (const float*)h8 + 2 * (size_t)n);
-    xr.assign((const float*)(h8 + 8 * (size_t)n), (const float*)(h8 + 8 * (size_t)n) + n);
-    st.assign(h8 + 12 * (size_t)n, h8 + 13 * (size_t)n);
-    ok.assign(h8 + 13 * (size_t)n, h8 + 14 * (size_t)n);
-    int k = *(const int32_t*)(h8 + o);
-    k = std::max(0, std::min(k, m));
-    const uint8_t* nb = h8 + o + 16;
-    nuv.assign((const float*)nb, (const float*)nb + 2 * (size_t)k);
-    nxr.assign((const float*)(nb + 8 * (size_t)m), (const float*)(nb + 8 * (size_t)m) + k);
-    nok.assign(nb + 16 * (size_t)m, nb + 16 * (size_t)m + k);
     return ME_OK;
   }
-  // The corner detector queued on the front end: tracked features in device memory (n = 0: none),
-  // new-feature block n8 (count (16 B) | uv | xr | lo | ok)
-  int new_corners(const Imgs& im, const float* uv, const uint8_t* st, const uint8_t* ok, int n, uint8_t* n8) {
-    const int m = std::max(cfg.n_feats, 1);
-    const me_corner_params cp{cfg.corner_win, cfg.corner_min_eig};
-    return me_vo_new_corners(tctx, im.L, cfg.width, cfg.height, cfg.width, n ? uv : nullptr, n ? st : nullptr,
-                             n ? ok : nullptr, n, (float)kMargin, nx, ny, cw, ch, cfg.n_feats, cfg.d_min, &cp,
-                             (float*)(n8 + 16), (int32_t*)(n8 + 16 + 12 * (size_t)m), (int32_t*)n8);
+  // GPUBackend.klt_match_new: tracked features' matcher, the cells they leave
+  // empty, the new features' matcher -- one submission, one round trip
+  int klt_match_new(const me_vo::KltIn& in, const Imgs& im, const std::vector<int32_t>& lo,
+                    const std::vector<uint8_t>& dvalid, int t, int nd, int nd_new, std::vector<float>& uv,
+                    std::vector<uint8_t>& st, std::vector<float>& xr, std::vector<uint8_t>& ok, std::vector<float>& nuv,
+                    std::vector<float>& nxr, std::vector<uint8_t>& nok) {
+    const int n = (int)in.n;
+    const me_vo::Res res{in.n};
+    const me_vo::NewFeats nf{(size_t)std::max(cfg.n_feats, 1)};
+    void *hp, *dl, *dres, *dn, *ho;
+    VL_TRY(hbuf("lo", 5 * in.n, &hp), "match");
+    std::memcpy(hp, lo.data(), 4 * in.n);
+    std::memcpy((uint8_t*)hp + 4 * in.n, dvalid.data(), n);
+    VL_TRY(dbuf("lo", 5 * in.n, &dl), "match");
+    VL_TRY(me_memcpy_async(tctx, dl, hp, 5 * in.n), "match H2D");
+    VL_TRY(dbuf("res", res.size(), &dres), "match");
+    VL_TRY(epi_match(im, res.uv(dres), (const int32_t*)dl, (const uint8_t*)dl + 4 * in.n, res.status(dres), n, nd, 0,
+                     res.xr(dres), res.ok(dres)),
+           "me_mi_epipolar_match");
+    if (gate) {  // in place on the ok byte the detector below and the host's good mask read
+      void* d_in = dev["klt_in"].p;
+      VL_TRY(me_motion_gate(tctx, in.pts(d_in), in.xr(d_in), res.uv(dres), res.xr(dres), res.status(dres), res.ok(dres),
+                            n, f, cx, cy, cfg.baseline, cfg.width, cfg.height, (float)kMargin, t, &gate_params,
+                            res.ok(dres), nullptr, nullptr),
+             "me_motion_gate");
+    }
+    VL_TRY(dbuf("new", nf.size(), &dn), "match");
+    if (const int rc = new_features(im, dres, n, t, nd_new, nf, dn)) return rc;
+    const size_t o = res.o_new_mirror();
+    VL_TRY(hbuf("out", o + nf.size(), &ho), "match");
+    VL_TRY(me_memcpy_async(tctx, ho, dres, res.size()), "match D2H");
+    VL_TRY(me_memcpy_async(tctx, (uint8_t*)ho + o, dn, nf.size()), "match D2H");
+    VL_TRY(timed_wait(0, [&] { return me_synchronize(tctx); }), "klt_match_new");
+    uv.assign(res.uv(ho), res.uv(ho) + 2 * in.n);
+    xr.assign(res.xr(ho), res.xr(ho) + in.n);
+    st.assign(res.status(ho), res.status(ho) + in.n);
+    ok.assign(res.ok(ho), res.ok(ho) + in.n);
+    nf.decode((uint8_t*)ho + o, nuv, nxr, nok);
+    return ME_OK;
   }
   // A keyframe without tracked features under the corner detector: the detector and the new
   // features' matcher in one submission (klt_match_new without its tracked half)
   int corners_match(const Imgs& im, int nd_new, std::vector<float>& nuv, std::vector<float>& nxr,
                     std::vector<uint8_t>& nok) {
+    const me_vo::NewFeats nf{(size_t)std::max(cfg.n_feats, 1)};
     void *dn, *ho;
-    const int m = std::max(cfg.n_feats, 1);
-    VL_TRY(dbuf("new", 16 + 17 * (size_t)m, &dn), "match");
-    uint8_t* n8 = (uint8_t*)dn;
-    VL_TRY(new_corners(im, nullptr, nullptr, nullptr, 0, n8), "me_vo_new_corners");
-    VL_TRY(epi_match_count(im, (const float*)(n8 + 16), (const int32_t*)(n8 + 16 + 12 * (size_t)m),
-                           (const int32_t*)n8, m, nd_new, (float*)(n8 + 16 + 8 * (size_t)m), n8 + 16 + 16 * (size_t)m),
-           "me_mi_epipolar_match_count");
-    VL_TRY(hbuf("out", 16 + 17 * (size_t)m, &ho), "match");
-    VL_TRY(me_memcpy_async(tctx, ho, dn, 16 + 17 * (size_t)m), "match D2H");
+    VL_TRY(dbuf("new", nf.size(), &dn), "match");
+    if (const int rc = new_features(im, nullptr, 0, 0, nd_new, nf, dn)) return rc;
+    VL_TRY(hbuf("out", nf.size(), &ho), "match");
+    VL_TRY(me_memcpy_async(tctx, ho, dn, nf.size()), "match D2H");
     VL_TRY(timed_wait(1, [&] { return me_synchronize(tctx); }), "corners_match");
-    const uint8_t* h8 = (const uint8_t*)ho;
-    int k = *(const int32_t*)h8;
-    k = std::max(0, std::min(k, m));
-    const uint8_t* nb = h8 + 16;
-    nuv.assign((const float*)nb, (const float*)nb + 2 * (size_t)k);
-    nxr.assign((const float*)(nb + 8 * (size_t)m), (const float*)(nb + 8 * (size_t)m) + k);
-    nok.assign(nb + 16 * (size_t)m, nb + 16 * (size_t)m + k);
+    nf.decode(ho, nuv, nxr, nok);
     return ME_OK;
   }
   // GPUBackend.match: the first keyframe's new features (uniqueness test)
@@ -859,22 +765,20 @@ struct me_vo_loop {
     xr.assign(n, 0.0f);
     ok.assign(n, 0);
     if (n == 0) return ME_OK;
+    const me_vo::FirstMatch fm{(size_t)n};
     void *hp, *d, *ho;
-    VL_TRY(hbuf("m_in", 12 * (size_t)n, &hp), "match");
-    std::memcpy(hp, uv.data(), 8 * (size_t)n);
-    int32_t* lo = (int32_t*)((uint8_t*)hp + 8 * (size_t)n);
-    for (int i = 0; i < n; ++i) lo[i] = cfg.d_min;
-    VL_TRY(dbuf("m", 17 * (size_t)n, &d), "match");
-    VL_TRY(me_memcpy_async(tctx, d, hp, 12 * (size_t)n), "match H2D");
-    uint8_t* d8 = (uint8_t*)d;
-    VL_TRY(epi_match(im, (const float*)d, (const int32_t*)(d8 + 8 * (size_t)n), nullptr, nullptr, n, nd, 1,
-                     (float*)(d8 + 12 * (size_t)n), d8 + 16 * (size_t)n),
-           "me_mi_epipolar_match");
-    VL_TRY(hbuf("m_out", 5 * (size_t)n, &ho), "match");
-    VL_TRY(me_memcpy_async(tctx, ho, d8 + 12 * (size_t)n, 5 * (size_t)n), "match D2H");
+    VL_TRY(hbuf("m_in", fm.o_xr(), &hp), "match");  // (the uploaded part: uv | lo)
+    std::memcpy(fm.uv(hp), uv.data(), 8 * fm.n);
+    std::fill_n(fm.lo(hp), n, (int32_t)cfg.d_min);
+    VL_TRY(dbuf("m", fm.size(), &d), "match");
+    VL_TRY(me_memcpy_async(tctx, d, hp, fm.o_xr()), "match H2D");
+    VL_TRY(epi_match(im, fm.uv(d), fm.lo(d), nullptr, nullptr, n, nd, 1, fm.xr(d), fm.ok(d)), "me_mi_epipolar_match");
+    const size_t nb = fm.size() - fm.o_xr();  // (the part read back: x_r | ok)
+    VL_TRY(hbuf("m_out", nb, &ho), "match");
+    VL_TRY(me_memcpy_async(tctx, ho, fm.xr(d), nb), "match D2H");
     VL_TRY(timed_wait(1, [&] { return me_synchronize(tctx); }), "match");
-    std::memcpy(xr.data(), ho, 4 * (size_t)n);
-    std::memcpy(ok.data(), (uint8_t*)ho + 4 * (size_t)n, n);
+    std::memcpy(xr.data(), ho, 4 * fm.n);
+    std::memcpy(ok.data(), (uint8_t*)ho + (fm.o_ok() - fm.o_xr()), n);
     return ME_OK;
   }
 
@@ -1287,16 +1191,17 @@ struct me_vo_loop {
   }
 
   // pipeline.WindowedStereoVO.process (the steps are numbered as there)
-  int process(int t, const uint8_t* left, const uint8_t* right, me_mem mem) {
+  // im: keyframe t's prepared pair; kf_guess (me_vo_loop_push): the tracker's guess, ahead of klt_predict's
+  int process(int t, const Imgs& im, const std::vector<float>* kf_guess = nullptr) {
     const double t_in = now_s();
     const double w0 = wait_s;
-    VL_TRY(frame_images(t, left, right, mem), "images");
-    const Imgs im = imgs[t];
+    imgs[t] = im;
     // 1. KLT of the active tracks, queued first (it needs only frame t-1's features)
     std::vector<int64_t> act;
     for (size_t i = 0; i < ntab(); ++i)
       if (active[i]) act.push_back((int64_t)i);
     const bool klt = has_prev && !act.empty();
+    me_vo::KltIn kin{0, false, false};  // the tracker's upload, which the gate of step 4 reads again
     if (klt) {
       const FrameObs& po = obs[prev_t];
       std::vector<float> pts(2 * act.size()), pxr(gate ? act.size() : 0);
@@ -1330,9 +1235,9 @@ struct me_vo_loop {
           guess[2 * k + 1] = Z > 0 ? (float)(f * Yc / Z + cy) : nan;
         }
       }
-      VL_TRY(klt_submit(imgs[prev_t], im, pts, kf_guess ? kf_guess : (klt_predict ? &guess : nullptr),
-                        gate ? &pxr : nullptr),
-             "klt");
+      if (!kf_guess && klt_predict) kf_guess = &guess;
+      kin = me_vo::KltIn{act.size(), kf_guess != nullptr, gate};
+      VL_TRY(klt_submit(imgs[prev_t], im, kin, pts, kf_guess, gate ? &pxr : nullptr), "klt");
     }
     // 2. pops of frame t-1's completion
     if (has_pending) pop(pending.t + 1 - cfg.window);
@@ -1366,7 +1271,7 @@ struct me_vo_loop {
       }
       std::vector<float> uv, xr_all;
       std::vector<uint8_t> st, ok;
-      VL_TRY(klt_match_new(n, im, lo, dvalid, t, 2 * kHalf + 1, nd_new, uv, st, xr_all, ok, nuv, nxr, nok),
+      VL_TRY(klt_match_new(kin, im, lo, dvalid, t, 2 * kHalf + 1, nd_new, uv, st, xr_all, ok, nuv, nxr, nok),
              "klt_match_new");
       for (int k = 0; k < n; ++k) {
         const bool good = st[k] == 1 && in_margin(uv[2 * k], uv[2 * k + 1]) && ok[k];
@@ -1502,154 +1407,96 @@ struct me_vo_loop {
     return ME_OK;
   }
   // ------------------------------------------------------------ me_vo_loop_push (pipeline.WindowedStereoVO.push)
-  size_t kf_info_offset() const { return 16 * (((fpose ? 30 : 26) * (size_t)kf_n + 15) / 16); }
-  size_t kf_info_bytes() const { return fpose ? 160 : 32; }  // the keyframe block, and the pose block behind it
-  size_t kf_alive_offset() const { return (fpose ? 28 : 24) * (size_t)kf_n; }  // alive (n), then status (n)
-  // The front-end chain of one pushed frame, once, into push_slot[slot]: upload or copy, remap, CLAHE
-  int prepare_pushed(int slot, const uint8_t* L, const uint8_t* R, me_mem mem, Imgs& im) {
-    const size_t npx = (size_t)cfg.width * cfg.height;
-    void*& p = push_slot[slot];
-    if (p == nullptr) VL_TRY(me_malloc(tctx, &p, 2 * npx), "malloc");
-    uint8_t* o = (uint8_t*)p;
-    im.L = o;
-    im.R = o + npx;
-    if (rectify) {
-      const size_t nl = (size_t)raw_w[0] * raw_h[0], nr = (size_t)raw_w[1] * raw_h[1];
-      if (mem != ME_DEVICE) {
-        VL_TRY(me_memcpy_async(tctx, rect_raw, L, nl), "image upload");
-        VL_TRY(me_memcpy_async(tctx, (uint8_t*)rect_raw + nl, R, nr), "image upload");
-        L = (const uint8_t*)rect_raw;
-        R = L + nl;
-      }
-      VL_TRY(me_remap_q5(tctx, ME_DEVICE, L, raw_w[0], raw_h[0], raw_w[0], (const int32_t*)rect_map[0], cfg.width,
-                         cfg.height, rect_border, o, cfg.width, nullptr),
-             "me_remap_q5");
-      VL_TRY(me_remap_q5(tctx, ME_DEVICE, R, raw_w[1], raw_h[1], raw_w[1], (const int32_t*)rect_map[1], cfg.width,
-                         cfg.height, rect_border, o + npx, cfg.width, nullptr),
-             "me_remap_q5");
-    } else if (equalise && mem == ME_DEVICE) {  // (the caller's images are never written: equalised into the slot)
-      VL_TRY(me_clahe(tctx, ME_DEVICE, L, cfg.width, cfg.height, cfg.width, &eq_params, o, cfg.width, nullptr), "me_clahe");
-      VL_TRY(me_clahe(tctx, ME_DEVICE, R, cfg.width, cfg.height, cfg.width, &eq_params, o + npx, cfg.width, nullptr),
-             "me_clahe");
-      return ME_OK;
-    } else {
-      VL_TRY(me_memcpy_async(tctx, o, L, npx), "image upload");
-      VL_TRY(me_memcpy_async(tctx, o + npx, R, npx), "image upload");
-    }
-    if (equalise) {  // in place: the slot is the loop's
-      VL_TRY(me_clahe(tctx, ME_DEVICE, o, cfg.width, cfg.height, cfg.width, &eq_params, o, cfg.width, nullptr), "me_clahe");
-      VL_TRY(me_clahe(tctx, ME_DEVICE, o + npx, cfg.width, cfg.height, cfg.width, &eq_params, o + npx, cfg.width, nullptr),
-             "me_clahe");
-    }
-    return ME_OK;
-  }
   // The state seeded from keyframe t's active tracks: their left positions, in the order the next klt_submit
   // uploads them (table order)
   int kf_seed(int t) {
     const FrameObs& po = obs[t];
+    std::vector<float> xr;
     kf_ref.clear();
     for (size_t i = 0; i < ntab(); ++i) {
       if (!active[i]) continue;
       const size_t pos = (size_t)(std::lower_bound(po.ids.begin(), po.ids.end(), ids[i]) - po.ids.begin());
       kf_ref.push_back(po.feats[4 * pos]);
       kf_ref.push_back(po.feats[4 * pos + 1]);
+      if (fpose) xr.push_back(po.feats[4 * pos + 2]);
     }
     kf_n = (int)(kf_ref.size() / 2);
     kf_gap = 0;
-    const size_t n = (size_t)kf_n;
+    const me_vo::Kf kf{(size_t)kf_n, fpose};
     void *hp, *d;
-    VL_TRY(dbuf("kf", kf_info_offset() + kf_info_bytes(), &d), "kf");
-    if (fpose) {
-      // one copy of the whole block: x_r rides beside the positions, the pose block behind the info block is
-      // zeroed (valid = 0: the first frame after the keyframe starts at identity)
-      const size_t total = kf_info_offset() + 160;
-      VL_TRY(hbuf("kf_in", total, &hp), "kf");
-      std::memset(hp, 0, total);
-      std::memcpy(hp, kf_ref.data(), 8 * n);
-      std::memcpy((uint8_t*)hp + 8 * n, kf_ref.data(), 8 * n);
-      float* xr = (float*)((uint8_t*)hp + 24 * n);
-      size_t k = 0;
-      for (size_t i = 0; i < ntab(); ++i) {
-        if (!active[i]) continue;
-        const size_t pos = (size_t)(std::lower_bound(po.ids.begin(), po.ids.end(), ids[i]) - po.ids.begin());
-        xr[k++] = po.feats[4 * pos + 2];
-      }
-      std::memset((uint8_t*)hp + 28 * n, 1, n);
-      VL_TRY(me_memcpy_async(tctx, d, hp, total), "kf H2D");
-      return ME_OK;
-    }
-    if (n == 0) return ME_OK;
-    VL_TRY(hbuf("kf_in", 25 * n, &hp), "kf");
-    std::memcpy(hp, kf_ref.data(), 8 * n);
-    std::memcpy((uint8_t*)hp + 8 * n, kf_ref.data(), 8 * n);
-    std::memset((uint8_t*)hp + 24 * n, 1, n);
-    // (new_uv's bytes ride along in the one copy: the tracker writes them before they are read)
-    VL_TRY(me_memcpy_async(tctx, d, hp, 25 * n), "kf H2D");
+    VL_TRY(dbuf("kf", kf.size(), &d), "kf");
+    // one copy.  With the frame pose the whole block: x_r rides beside the positions, the pose block behind the
+    // info block is zeroed (valid = 0: the first frame after the keyframe starts at identity).  Without it up to
+    // alive: new_uv's bytes ride along, the tracker writes them before they are read
+    const size_t total = fpose ? kf.size() : kf.o_status();
+    if (total == 0) return ME_OK;
+    VL_TRY(hbuf("kf_in", total, &hp), "kf");
+    if (fpose) std::memset(hp, 0, total);
+    std::memcpy(kf.ref(hp), kf_ref.data(), 8 * kf.n);
+    std::memcpy(kf.cur(hp), kf_ref.data(), 8 * kf.n);
+    if (fpose) std::memcpy(kf.ref_xr(hp), xr.data(), 4 * kf.n);
+    std::memset(kf.alive(hp), 1, kf.n);
+    VL_TRY(me_memcpy_async(tctx, d, hp, total), "kf H2D");
     return ME_OK;
   }
   // One pushed frame: the loop's tracker (not guided) pv -> cur at cur_uv, me_kf_update behind it, the info block back
   int kf_track(const Imgs& pv, const Imgs& cur, unsigned char* info_out) {
-    const size_t n = (size_t)kf_n, o_info = kf_info_offset(), o_al = kf_alive_offset(), nb = kf_info_bytes();
+    const me_vo::Kf kf{(size_t)kf_n, fpose};
+    const int n = kf_n;
     void *d, *ho;
-    VL_TRY(dbuf("kf", o_info + nb, &d), "kf");  // (sized by the seed: it does not grow here)
-    uint8_t* b = (uint8_t*)d;
-    if (n) {
-      me_klt_params kp;
-      me_klt_default_params(&kp);
-      if (cfg.klt_fb_max > 0.0)
-        VL_TRY(me_klt_track_fb(tctx, ME_DEVICE, pv.L, cur.L, cfg.width, cfg.height, cfg.width, (const float*)(b + 8 * n),
-                               (float*)(b + 16 * n), b + o_al + n, nullptr, (int)n, &kp, cfg.klt_fb_max),
-               "me_klt_track_fb");
-      else
-        VL_TRY(me_klt_track(tctx, ME_DEVICE, pv.L, cur.L, cfg.width, cfg.height, cfg.width, (const float*)(b + 8 * n),
-                            (float*)(b + 16 * n), b + o_al + n, (int)n, &kp),
-               "me_klt_track");
-    }
-    VL_TRY(me_kf_update(tctx, n ? (const float*)b : nullptr, n ? (float*)(b + 8 * n) : nullptr, n ? b + o_al : nullptr,
-                        n ? (const float*)(b + 16 * n) : nullptr, n ? b + o_al + n : nullptr, (int)n, cfg.width,
-                        cfg.height, (float)kMargin, kf_gap, &kf_params, b + o_info),
+    VL_TRY(dbuf("kf", kf.size(), &d), "kf");  // (sized by the seed: it does not grow here)
+    if (n)
+      if (const int rc = track(pv, cur, kf.cur(d), nullptr, kf.nw(d), kf.status(d), n)) return rc;
+    VL_TRY(me_kf_update(tctx, n ? kf.ref(d) : nullptr, n ? kf.cur(d) : nullptr, n ? kf.alive(d) : nullptr,
+                        n ? kf.nw(d) : nullptr, n ? kf.status(d) : nullptr, n, cfg.width, cfg.height, (float)kMargin,
+                        kf_gap, &kf_params, kf.info(d)),
            "me_kf_update");
     if (fpose)  // right behind the update, from the previous frame's pose (start == info)
-      VL_TRY(me_frame_pose(tctx, n ? (const float*)b : nullptr, n ? (const float*)(b + 24 * n) : nullptr,
-                           n ? (const float*)(b + 8 * n) : nullptr, n ? b + o_al : nullptr, (int)n, cfg.K[0], cfg.K[2],
-                           cfg.K[5], cfg.baseline, &fpose_params, b + o_info + 32, nullptr, b + o_info + 32),
+      VL_TRY(me_frame_pose(tctx, n ? kf.ref(d) : nullptr, n ? kf.ref_xr(d) : nullptr, n ? kf.cur(d) : nullptr,
+                           n ? kf.alive(d) : nullptr, n, cfg.K[0], cfg.K[2], cfg.K[5], cfg.baseline, &fpose_params,
+                           kf.pose_block(d), nullptr, kf.pose_block(d)),
              "me_frame_pose");
-    VL_TRY(hbuf("kf_out", nb, &ho), "kf");
-    VL_TRY(me_memcpy_async(tctx, ho, b + o_info, nb), "kf D2H");
+    VL_TRY(hbuf("kf_out", kf.info_bytes(), &ho), "kf");
+    VL_TRY(me_memcpy_async(tctx, ho, kf.info(d), kf.info_bytes()), "kf D2H");
     VL_TRY(me_synchronize(tctx), "kf_track");
-    std::memcpy(info_out, ho, nb);
+    std::memcpy(info_out, ho, kf.info_bytes());
     return ME_OK;
   }
   // The keyframe tracker's guess: cur_uv of the alive features, the keyframe's positions of the others
   int kf_read_guess(std::vector<float>& guess) {
-    const size_t n = (size_t)kf_n;
+    const me_vo::Kf kf{(size_t)kf_n, fpose};
     void *d, *ho;
-    VL_TRY(dbuf("kf", kf_info_offset() + kf_info_bytes(), &d), "kf");
-    const size_t nb = kf_alive_offset() - 7 * n;  // cur_uv | new_uv | (ref_xr |) alive
+    VL_TRY(dbuf("kf", kf.size(), &d), "kf");
+    const size_t nb = kf.o_status() - kf.o_cur();  // cur_uv | new_uv | (ref_xr |) alive
     VL_TRY(hbuf("kf_state", nb, &ho), "kf");
-    VL_TRY(me_memcpy_async(tctx, ho, (uint8_t*)d + 8 * n, nb), "kf D2H");
+    VL_TRY(me_memcpy_async(tctx, ho, kf.cur(d), nb), "kf D2H");
     VL_TRY(me_synchronize(tctx), "kf_guess");
     const float* cu = (const float*)ho;
-    const uint8_t* al = (const uint8_t*)ho + nb - n;
-    guess.resize(2 * n);
-    for (size_t k = 0; k < n; ++k) {
+    const uint8_t* al = (const uint8_t*)ho + (kf.o_alive() - kf.o_cur());
+    guess.resize(2 * kf.n);
+    for (size_t k = 0; k < kf.n; ++k) {
       guess[2 * k] = al[k] ? cu[2 * k] : kf_ref[2 * k];
       guess[2 * k + 1] = al[k] ? cu[2 * k + 1] : kf_ref[2 * k + 1];
     }
     return ME_OK;
   }
+  // A keyframe took pool slot `slot`: it is held for this keyframe and the next
+  void hold_keyframe(int slot) {
+    slot_kf[1] = slot_kf[0];
+    slot_kf[0] = slot;
+    slot_prev = -1;
+  }
   int push(const uint8_t* left, const uint8_t* right, me_mem mem, int* keyframe_t) {
     *keyframe_t = -1;
-    int slot = 0;
-    while (slot == push_prev || slot == push_kf[0] || slot == push_kf[1]) ++slot;  // (three held at the most: < 4)
+    const int slot = me_vo::pool_pick(slot_prev, slot_kf[0], slot_kf[1]);
     Imgs im;
-    VL_TRY(prepare_pushed(slot, left, right, mem, im), "images");
+    VL_TRY(prepare(left, right, mem, 8, true, slot, im), "images");
     ++n_pushed;
     std::vector<float> guess;
     bool guided = false;
     if (has_prev) {
       ++kf_gap;
-      const Imgs pv = push_prev >= 0 ? push_imgs : imgs[prev_t];
+      const Imgs pv = slot_prev >= 0 ? push_imgs : imgs[prev_t];
       alignas(8) unsigned char info[160] = {0};
       VL_TRY(kf_track(pv, im, info), "kf_track");
       int32_t flags;
@@ -1671,7 +1518,7 @@ struct me_vo_loop {
         fposes.push_back(r);
       }
       if (flags == 0) {  // no keyframe: the frame becomes the previous pushed frame, nothing else moves
-        push_prev = slot;
+        slot_prev = slot;
         push_imgs = im;
         return ME_OK;
       }
@@ -1681,16 +1528,21 @@ struct me_vo_loop {
       }
     }
     const int t = has_prev ? prev_t + 1 : 0;
-    imgs[t] = im;  // (frame_images finds the keyframe's pair prepared)
-    kf_guess = guided ? &guess : nullptr;
-    const int rc = process(t, nullptr, nullptr, ME_DEVICE);
-    kf_guess = nullptr;
-    if (rc != ME_OK) return rc;
-    push_kf[1] = push_kf[0];
-    push_kf[0] = slot;
-    push_prev = -1;
+    if (const int rc = process(t, im, guided ? &guess : nullptr)) return rc;
+    hold_keyframe(slot);
     VL_TRY(kf_seed(t), "kf_seed");
     *keyframe_t = t;
+    return ME_OK;
+  }
+  // me_vo_loop_process / me_vo_loop_process16 (bits 8 / 16): every frame is a keyframe, the pool's pick is t % 3
+  int keyframe(int t, const void* left, const void* right, me_mem mem, int bits) {
+    const double t_in = now_s();
+    const int slot = me_vo::pool_pick(-1, slot_kf[0], slot_kf[1]);
+    Imgs im;
+    VL_TRY(prepare(left, right, mem, bits, false, slot, im), "images");
+    host_s += now_s() - t_in;
+    if (const int rc = process(t, im)) return rc;
+    hold_keyframe(slot);
     return ME_OK;
   }
   int finish() {
@@ -1714,6 +1566,34 @@ struct me_vo_loop {
   }
 #undef VL_TRY
 };
+
+namespace {
+
+// A switch is set before the loop's first frame: refused (msg) once a keyframe went through, or a call failed
+bool started(me_vo_loop* v, const char* msg) {
+  if (v->has_prev || v->failed) v->err = msg;
+  return v->has_prev || v->failed;
+}
+
+// The checks the frame entries share, in this order: frames come through me_vo_loop_push or keyframes through
+// me_vo_loop_process*, never both; keyframes in order (a pushed frame has no t: the loop numbers its keyframes); no
+// earlier failure; one depth (bits 8 / 16) per loop, which is recorded
+int enter(me_vo_loop* v, const char* who, bool push, int t, int bits) {
+  const auto refuse = [&](const std::string& why) {
+    v->err = std::string(who) + ": " + why;
+    return ME_ERR_STATE;
+  };
+  if (!push && v->n_pushed > 0) return refuse("this loop's frames come through me_vo_loop_push");
+  if (!push && t != (v->has_prev ? v->prev_t + 1 : 0)) return refuse("keyframes must come in order 0, 1, 2, ...");
+  if (v->failed) return refuse("an earlier call failed (" + v->err + "); the loop state is undefined");
+  if (push ? v->has_prev && v->n_pushed == 0 : v->depth != 0 && v->depth != bits)
+    return refuse(std::string("this loop's keyframes come through ") +
+                  (v->depth == 16 ? "me_vo_loop_process16" : "me_vo_loop_process"));
+  v->depth = bits;
+  return ME_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -1782,10 +1662,8 @@ int me_vo_loop_set_match_lr(me_vo_loop* v, double lr_max) {
     v->err = "me_vo_loop_set_match_lr: match_lr_max must be >= 0 (0: no left-right check)";
     return ME_ERR_INVALID;
   }
-  if (v->has_prev || v->failed) {
-    v->err = "me_vo_loop_set_match_lr: match_lr_max is set before the first me_vo_loop_process";
+  if (started(v, "me_vo_loop_set_match_lr: match_lr_max is set before the first me_vo_loop_process"))
     return ME_ERR_STATE;
-  }
   v->match_lr = lr_max;
   return ME_OK;
 }
@@ -1797,10 +1675,8 @@ int me_vo_loop_set_motion_gate(me_vo_loop* v, const me_motion_gate_params* p) {
       v->err = std::string("me_vo_loop_set_motion_gate: ") + why;
       return ME_ERR_INVALID;
     }
-  if (v->has_prev || v->failed) {
-    v->err = "me_vo_loop_set_motion_gate: the rigid-motion gate is set before the first me_vo_loop_process";
+  if (started(v, "me_vo_loop_set_motion_gate: the rigid-motion gate is set before the first me_vo_loop_process"))
     return ME_ERR_STATE;
-  }
   v->gate = p != nullptr;
   if (p) v->gate_params = *p;
   return ME_OK;
@@ -1812,10 +1688,8 @@ int me_vo_loop_set_klt_predict(me_vo_loop* v, int on) {
     v->err = "me_vo_loop_set_klt_predict: on must be 0 or 1";
     return ME_ERR_INVALID;
   }
-  if (v->has_prev || v->failed) {
-    v->err = "me_vo_loop_set_klt_predict: guided tracking is set before the first me_vo_loop_process";
+  if (started(v, "me_vo_loop_set_klt_predict: guided tracking is set before the first me_vo_loop_process"))
     return ME_ERR_STATE;
-  }
   v->klt_predict = on == 1;
   return ME_OK;
 }
@@ -1830,10 +1704,8 @@ int me_vo_loop_set_rectify(me_vo_loop* v, const me_camera_model* left, const me_
     v->err = "me_vo_loop_set_rectify: border must be in 0..255";
     return ME_ERR_INVALID;
   }
-  if (v->has_prev || v->failed) {
-    v->err = "me_vo_loop_set_rectify: rectification is set before the first me_vo_loop_process";
+  if (started(v, "me_vo_loop_set_rectify: rectification is set before the first me_vo_loop_process"))
     return ME_ERR_STATE;
-  }
   me_range range_("me_vo_loop_set_rectify");
   if (!left) {
     v->rectify_off();
@@ -1846,11 +1718,9 @@ int me_vo_loop_set_rectify(me_vo_loop* v, const me_camera_model* left, const me_
 
 int me_vo_loop_set_equalise(me_vo_loop* v, const me_clahe_params* p) {
   if (!v) return ME_ERR_INVALID;
-  if (v->has_prev || v->failed) {
-    v->err = "me_vo_loop_set_equalise: equalisation is set before the first me_vo_loop_process";
+  if (started(v, "me_vo_loop_set_equalise: equalisation is set before the first me_vo_loop_process"))
     return ME_ERR_STATE;
-  }
-  v->equalise_off();
+  v->equalise = false;
   if (!p) return ME_OK;
   if (const char* why = me_clahe_check(p, v->cfg.width, v->cfg.height)) {
     v->err = std::string("me_vo_loop_set_equalise: ") + why;
@@ -1863,10 +1733,8 @@ int me_vo_loop_set_equalise(me_vo_loop* v, const me_clahe_params* p) {
 
 int me_vo_loop_set_tonemap(me_vo_loop* v, const me_tonemap_params* p) {
   if (!v) return ME_ERR_INVALID;
-  if (v->has_prev || v->failed) {
-    v->err = "me_vo_loop_set_tonemap: the tone map is set before the first me_vo_loop_process";
+  if (started(v, "me_vo_loop_set_tonemap: the tone map is set before the first me_vo_loop_process"))
     return ME_ERR_STATE;
-  }
   v->tonemap_off();
   if (!p) return ME_OK;
   if (v->kf_on) {
@@ -1894,10 +1762,8 @@ int me_vo_loop_set_keyframe_select(me_vo_loop* v, const me_kf_params* p) {
       return ME_ERR_INVALID;
     }
   }
-  if (v->has_prev || v->failed) {
-    v->err = "me_vo_loop_set_keyframe_select: keyframe selection is set before the first frame";
+  if (started(v, "me_vo_loop_set_keyframe_select: keyframe selection is set before the first frame"))
     return ME_ERR_STATE;
-  }
   v->kf_on = p != nullptr;
   if (p) v->kf_params = *p;
   if (!p) v->fpose = false;  // (the frame pose refines pushed frames: it goes with the switch it needs)
@@ -1944,15 +1810,7 @@ int me_vo_loop_push(me_vo_loop* v, const uint8_t* left, const uint8_t* right, me
     v->err = "me_vo_loop_push: camera frames need me_vo_loop_set_keyframe_select";
     return ME_ERR_STATE;
   }
-  if (v->failed) {
-    v->err = "me_vo_loop_push: an earlier call failed (" + v->err + "); the loop state is undefined";
-    return ME_ERR_STATE;
-  }
-  if (v->has_prev && v->n_pushed == 0) {
-    v->err = "me_vo_loop_push: this loop's keyframes come through me_vo_loop_process";
-    return ME_ERR_STATE;
-  }
-  v->depth = 8;
+  if (const int rc = enter(v, "me_vo_loop_push", true, 0, 8)) return rc;
   me_range range_("me_vo_loop_push");
   const int rc = v->push(left, right, mem, keyframe_t);
   if (rc != ME_OK) v->failed = true;
@@ -1961,25 +1819,9 @@ int me_vo_loop_push(me_vo_loop* v, const uint8_t* left, const uint8_t* right, me
 
 int me_vo_loop_process(me_vo_loop* v, int t, const uint8_t* left, const uint8_t* right, me_mem mem) {
   if (!v || !left || !right) return ME_ERR_INVALID;
-  if (v->n_pushed > 0) {
-    v->err = "me_vo_loop_process: this loop's frames come through me_vo_loop_push";
-    return ME_ERR_STATE;
-  }
-  if (t != (v->has_prev ? v->prev_t + 1 : 0)) {
-    v->err = "me_vo_loop_process: keyframes must come in order 0, 1, 2, ...";
-    return ME_ERR_STATE;
-  }
-  if (v->failed) {
-    v->err = "me_vo_loop_process: an earlier call failed (" + v->err + "); the loop state is undefined";
-    return ME_ERR_STATE;
-  }
-  if (v->depth == 16) {
-    v->err = "me_vo_loop_process: this loop's keyframes come through me_vo_loop_process16";
-    return ME_ERR_STATE;
-  }
-  v->depth = 8;
+  if (const int rc = enter(v, "me_vo_loop_process", false, t, 8)) return rc;
   me_range range_("me_vo_loop_process");
-  const int rc = v->process(t, left, right, mem);
+  const int rc = v->keyframe(t, left, right, mem, 8);
   if (rc != ME_OK) v->failed = true;  // the loop may have stopped half-way through a keyframe
   return rc;
 }
@@ -1990,25 +1832,9 @@ int me_vo_loop_process16(me_vo_loop* v, int t, const uint16_t* left, const uint1
     v->err = "me_vo_loop_process16: 16-bit keyframes need me_vo_loop_set_tonemap";
     return ME_ERR_STATE;
   }
-  if (t != (v->has_prev ? v->prev_t + 1 : 0)) {
-    v->err = "me_vo_loop_process16: keyframes must come in order 0, 1, 2, ...";
-    return ME_ERR_STATE;
-  }
-  if (v->failed) {
-    v->err = "me_vo_loop_process16: an earlier call failed (" + v->err + "); the loop state is undefined";
-    return ME_ERR_STATE;
-  }
-  if (v->depth == 8) {
-    v->err = "me_vo_loop_process16: this loop's keyframes come through me_vo_loop_process";
-    return ME_ERR_STATE;
-  }
-  v->depth = 16;
+  if (const int rc = enter(v, "me_vo_loop_process16", false, t, 16)) return rc;
   me_range range_("me_vo_loop_process16");
-  const uint8_t *l8 = nullptr, *r8 = nullptr;
-  int rc = v->tonemap_pair(t, left, right, mem, &l8, &r8);
-  v->own_device_pair = true;
-  if (rc == ME_OK) rc = v->process(t, l8, r8, ME_DEVICE);
-  v->own_device_pair = false;
+  const int rc = v->keyframe(t, left, right, mem, 16);
   if (rc != ME_OK) v->failed = true;
   return rc;
 }

@@ -821,103 +821,92 @@ class GPUBackend(Backend):
         tonemap_device(self.tctx, self.tonemapper, self._tm_dev[1], d_right, shape_r[1], shape_r[0], oR)
         return oL, oR
 
-    def _rectified(self, t, d_left, d_right, raw):
-        """Handle of keyframe t's rectified pair: two remaps of the raw device
-        images queued on the front-end stream into buffers of the backend's;
-        `raw` (buffers to free, or the caller's tensors) lives until release(t)."""
-        rect = self.rectifier
-        shape = rect.out.shape
-        n = shape[0] * shape[1]
-        oL, oR = self.tctx.malloc(n), self.tctx.malloc(n)
-        rect.apply_device(self.tctx, d_left, d_right, oL, oR)
-        self._equalise(oL, oR, oL, oR, shape)  # (in place: the rectified buffers are the backend's)
-        ph = np.lib.stride_tricks.as_strided(np.zeros(1, np.uint8), shape=shape, strides=(0, 0))  # shape only
-        self._raw[t] = raw
-        h = (oL, oR, shape, ph, ph)
-        self._imgs[t] = h
-        return h
+    def _rectified(self, d_left, d_right):
+        """Two remaps of raw device images queued on the front-end stream into new buffers of the backend's."""
+        shape = self.rectifier.out.shape
+        oL, oR = self.tctx.malloc(shape[0] * shape[1]), self.tctx.malloc(shape[0] * shape[1])
+        self.rectifier.apply_device(self.tctx, d_left, d_right, oL, oR)
+        return oL, oR
 
     def _equalise(self, d_left, d_right, d_out_left, d_out_right, shape):
-        """With the switch on: two me_clahe queued on the front-end stream, dense device images."""
-        if self.equaliser is not None:
-            from .equalise import clahe_device
+        """Two me_clahe queued on the front-end stream, dense device images."""
+        from .equalise import clahe_device
 
-            clahe_device(self.tctx, self.equaliser, d_left, shape[1], shape[0], d_out_left)
-            clahe_device(self.tctx, self.equaliser, d_right, shape[1], shape[0], d_out_right)
+        clahe_device(self.tctx, self.equaliser, d_left, shape[1], shape[0], d_out_left)
+        clahe_device(self.tctx, self.equaliser, d_right, shape[1], shape[0], d_out_right)
+
+    def _chain(self, t, pair, shape_l, shape_r, wide, owned, keep=(), host=None):
+        """Frame t's handle from a device pair: _tonemapped (wide: uint16) ->
+        _rectified -> _equalise, each with its switch.  owned: the pair is the
+        backend's; such a pair is equalised in place and freed at release(t),
+        at once or as one of the buffers behind the final pair (_raw).  The
+        caller's (keep: the tensors, referenced until release(t)) is never
+        written: it is equalised into new buffers, and with no stage on it is
+        the handle's pair as it is (6-tuple).  host: the host images behind a
+        pair uploaded as it is."""
+        behind = []
+        shape = shape_l
+        if wide:
+            behind += pair if owned else ()
+            pair, owned = self._tonemapped(pair[0], pair[1], shape_l, shape_r), True
+        if self.rectifier is not None:
+            behind += pair if owned else ()
+            pair, owned, shape = self._rectified(*pair), True, self.rectifier.out.shape
+        if self.equaliser is not None:
+            n = shape[0] * shape[1]
+            out = pair if owned else (self.tctx.malloc(n), self.tctx.malloc(n))
+            self._equalise(pair[0], pair[1], out[0], out[1], shape)
+            pair, owned = out, True
+        ph = np.lib.stride_tricks.as_strided(np.zeros(1, np.uint8), shape=shape, strides=(0, 0))  # shape only
+        if owned:
+            h = (pair[0], pair[1], shape) + (host or (ph, ph))
+            if behind or keep:
+                self._raw[t] = tuple(behind) + tuple(keep)
+        else:
+            h = (pair[0], pair[1], shape, ph, ph, tuple(keep))
+        self._imgs[t] = h
+        return h
 
     def frame_images(self, t, left, right):
         if t in self._imgs:
             return self._imgs[t]
-        if np.asarray(left).dtype == np.uint16:  # tone-mapped first; the 8-bit pair is the backend's own
+        who = "GPUBackend.frame_images"
+        wide = np.asarray(left).dtype == np.uint16  # tone-mapped first; the 8-bit pair is the backend's own
+        if wide:
             L, R = np.ascontiguousarray(left), np.asarray(right)
             if R.dtype != np.uint16:
-                raise ValueError(f"GPUBackend.frame_images: left is uint16, right {R.dtype}")
+                raise ValueError(f"{who}: left is uint16, right {R.dtype}")
             R = np.ascontiguousarray(R)
-            self._check_wide(L.shape, R.shape, "GPUBackend.frame_images")
-            d16 = (self.tctx.malloc(L.nbytes), self.tctx.malloc(R.nbytes))
-            self.tctx.h2d(d16[0], L)
-            self.tctx.h2d(d16[1], R)
-            dL, dR = self._tonemapped(d16[0], d16[1], L.shape, R.shape)
+            self._check_wide(L.shape, R.shape, who)
+        else:
+            L, R = np.ascontiguousarray(left, np.uint8), np.ascontiguousarray(right, np.uint8)
             if self.rectifier is not None:
-                return self._rectified(t, dL, dR, (dL, dR) + d16)
-            self._equalise(dL, dR, dL, dR, L.shape)
-            ph = np.lib.stride_tricks.as_strided(np.zeros(1, np.uint8), shape=L.shape, strides=(0, 0))  # shape only
-            self._raw[t] = d16
-            h = (dL, dR, L.shape, ph, ph)
-            self._imgs[t] = h
-            return h
-        L = np.ascontiguousarray(left, np.uint8)
-        R = np.ascontiguousarray(right, np.uint8)
+                self.rectifier.check_raw(L.shape, R.shape, who)
         # (on the front-end context: the BA context may be in use by the enqueue worker)
-        dL, dR = self.tctx.malloc(L.nbytes), self.tctx.malloc(R.nbytes)
-        self.tctx.h2d(dL, L)
-        self.tctx.h2d(dR, R)
-        if self.rectifier is not None:
-            self.rectifier.check_raw(L.shape, R.shape, "GPUBackend.frame_images")
-            return self._rectified(t, dL, dR, (dL, dR))
-        self._equalise(dL, dR, dL, dR, L.shape)  # (in place: the uploaded copies are the backend's)
-        h = (dL, dR, L.shape, L, R)
-        self._imgs[t] = h
-        return h
+        pair = self.tctx.malloc(L.nbytes), self.tctx.malloc(R.nbytes)
+        self.tctx.h2d(pair[0], L)
+        self.tctx.h2d(pair[1], R)
+        return self._chain(t, pair, L.shape, R.shape, wide, True,
+                           host=None if wide or self.rectifier is not None else (L, R))
 
     def frame_images_device(self, t, left, right):
         """Images already resident on the device (e.g. rendered there): `left`
-        / `right` expose data_ptr() and shape (torch uint8 tensors, kept
-        referenced until release(t))."""
+        / `right` expose data_ptr() and shape (torch uint8 tensors, or uint16
+        ones with the tone map; kept referenced until release(t))."""
         if t in self._imgs:
             return self._imgs[t]
-        if "uint16" in str(getattr(left, "dtype", "")):  # uint16 tensors: tone-mapped into buffers of the backend's
-            shape = tuple(left.shape)
+        who = "GPUBackend.frame_images_device"
+        wide = "uint16" in str(getattr(left, "dtype", ""))
+        if wide:
             for name, im in (("left", left), ("right", right)):
                 if "uint16" not in str(getattr(im, "dtype", "")) or not im.is_contiguous():
-                    raise ValueError(f"GPUBackend.frame_images_device: {name} must be a contiguous uint16 tensor, got "
+                    raise ValueError(f"{who}: {name} must be a contiguous uint16 tensor, got "
                                      f"{getattr(im, 'dtype', None)}")
-            self._check_wide(shape, tuple(right.shape), "GPUBackend.frame_images_device")
-            oL, oR = self._tonemapped(int(left.data_ptr()), int(right.data_ptr()), shape, tuple(right.shape))
-            if self.rectifier is not None:
-                return self._rectified(t, oL, oR, (oL, oR, left, right))
-            self._equalise(oL, oR, oL, oR, shape)
-            ph = np.lib.stride_tricks.as_strided(np.zeros(1, np.uint8), shape=shape, strides=(0, 0))  # shape only
-            self._raw[t] = (left, right)
-            h = (oL, oR, shape, ph, ph)
-            self._imgs[t] = h
-            return h
-        if self.rectifier is not None:
-            self.rectifier.check_raw(tuple(left.shape), tuple(right.shape), "GPUBackend.frame_images_device")
-            return self._rectified(t, int(left.data_ptr()), int(right.data_ptr()), (left, right))
-        shape = tuple(left.shape)
-        ph =np.lib.stride_tricks.as_strided(np.zeros(1, np.uint8), shape=shape, strides=(0, 0))  # shape only
-        if self.equaliser is not None:  # the caller's images are never written: equalised into buffers of the backend's
-            n = shape[0] * shape[1]
-            oL, oR = self.tctx.malloc(n), self.tctx.malloc(n)
-            self._equalise(int(left.data_ptr()), int(right.data_ptr()), oL, oR, shape)
-            self._raw[t] = (left, right)
-            h = (oL, oR, shape, ph, ph)
-            self._imgs[t] = h
-            return h
-        h = (int(left.data_ptr()), int(right.data_ptr()), shape, ph, ph, (left, right))
-        self._imgs[t] = h
-        return h
+            self._check_wide(tuple(left.shape), tuple(right.shape), who)
+        elif self.rectifier is not None:
+            self.rectifier.check_raw(tuple(left.shape), tuple(right.shape), who)
+        return self._chain(t, (int(left.data_ptr()), int(right.data_ptr())), tuple(left.shape), tuple(right.shape),
+                           wide, False, keep=(left, right))
 
     def release(self, t):
         h = self._imgs.pop(t, None)
