@@ -169,11 +169,96 @@ __device__ __forceinline__ void rotate(const double* aa, const double* X, double
   }
 }
 
+// One camera's entry of the rotation table (Bufs::rot, kRotStride doubles)
+// from its angle-axis vector: rotate()'s own expressions for R and M, formed
+// once per camera instead of once per observation.  Called where cameras are
+// written: plan_count_kernel (the starting cameras) and rot_step_body (the
+// candidates).
+__device__ __forceinline__ void rot_entry(const double* aa, double* e) {
+  const double t2 = aa[0] * aa[0] + aa[1] * aa[1] + aa[2] * aa[2];
+  double R[9], M[9];
+  if (t2 > kDblEps) {
+    const double th = sqrt(t2), c = cos(th), s = sin(th), ti = 1.0 / th;
+    const double w0 = aa[0] * ti, w1 = aa[1] * ti, w2 = aa[2] * ti;
+    const double oc = 1.0 - c;
+    const double Rr[9] = {c + oc * w0 * w0,      oc * w0 * w1 - s * w2, oc * w0 * w2 + s * w1,
+                          oc * w1 * w0 + s * w2, c + oc * w1 * w1,      oc * w1 * w2 - s * w0,
+                          oc * w2 * w0 - s * w1, oc * w2 * w1 + s * w0, c + oc * w2 * w2};
+    const double a0 = aa[0], a1 = aa[1], a2 = aa[2];
+    const double Wx[9] = {0, -a2, a1, a2, 0, -a0, -a1, a0, 0};
+    for (int i = 0; i < 9; ++i) R[i] = Rr[i];
+    for (int i = 0; i < 3; ++i)
+      for (int j = 0; j < 3; ++j) {
+        double acc = aa[i] * aa[j];
+        for (int k = 0; k < 3; ++k) acc += (R[k * 3 + i] - (i == k ? 1.0 : 0.0)) * Wx[k * 3 + j];
+        M[i * 3 + j] = acc / t2;
+      }
+  } else {
+    const double D[9] = {1, -aa[2], aa[1], aa[2], 1, -aa[0], -aa[1], aa[0], 1};  // I + [aa]x
+    for (int i = 0; i < 9; ++i) {
+      R[i] = D[i];
+      M[i] = 0.0;
+    }
+  }
+  for (int i = 0; i < 9; ++i) {
+    e[ROT_R + i] = R[i];
+    e[ROT_M + i] = M[i];
+  }
+  e[ROT_BRANCH] = t2 > kDblEps ? 1.0 : 0.0;
+  e[ROT_BRANCH + 1] = 0.0;
+}
+
+// rotate() from the camera's table entry: P = R X, dP/dX = R and
+// dP/dw = -(R [X]x) M; an entry of the small-angle branch keeps that branch's
+// meaning, P = X + aa x X (aa read back from R = I + [aa]x: rotate()'s bits),
+// dP/dX = I + [aa]x, dP/dw = -[X]x.
+__device__ __forceinline__ void rotate_tab(const double* e, const double* X, double* P, double* dPdw, double* dPdX) {
+  double R[9];
+  for (int i = 0; i < 9; ++i) R[i] = e[ROT_R + i];
+  if (e[ROT_BRANCH] != 0.0) {
+    for (int i = 0; i < 3; ++i) P[i] = R[i * 3 + 0] * X[0] + R[i * 3 + 1] * X[1] + R[i * 3 + 2] * X[2];
+    if (dPdX) {
+      double M[9];
+      for (int i = 0; i < 9; ++i) M[i] = e[ROT_M + i];
+      for (int i = 0; i < 9; ++i) dPdX[i] = R[i];
+      // -R [X]x M
+      double Xx[9] = {0, -X[2], X[1], X[2], 0, -X[0], -X[1], X[0], 0};
+      double RX[9];
+      for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) RX[i * 3 + j] = R[i * 3 + 0] * Xx[0 * 3 + j] + R[i * 3 + 1] * Xx[1 * 3 + j] + R[i * 3 + 2] * Xx[2 * 3 + j];
+      for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j)
+          dPdw[i * 3 + j] = -(RX[i * 3 + 0] * M[0 * 3 + j] + RX[i * 3 + 1] * M[1 * 3 + j] + RX[i * 3 + 2] * M[2 * 3 + j]);
+    }
+  } else {
+    const double a0 = R[7], a1 = R[2], a2 = R[3];
+    const double wx0 = a1 * X[2] - a2 * X[1], wx1 = a2 * X[0] - a0 * X[2], wx2 = a0 * X[1] - a1 * X[0];
+    P[0] = X[0] + wx0;
+    P[1] = X[1] + wx1;
+    P[2] = X[2] + wx2;
+    if (dPdX) {
+      for (int i = 0; i < 9; ++i) dPdX[i] = R[i];
+      double N[9] = {0, X[2], -X[1], -X[2], 0, X[0], X[1], -X[0], 0};  // -[X]x
+      for (int i = 0; i < 9; ++i) dPdw[i] = N[i];
+    }
+  }
+}
+
+// TAB: the camera's rotation comes from its table entry `rot` (rotate_tab: the
+// linearisation and the camera assembly), else from cam[3..5] (rotate: rot unused)
+template <bool TAB>
+__device__ __forceinline__ void rotate_cam(const double* cam, const double* rot, const double* X, double* P,
+                                           double* dPdw, double* dPdX) {
+  if constexpr (TAB) rotate_tab(rot, X, P, dPdw, dPdX);
+  else rotate(cam + 3, X, P, dPdw, dPdX);
+}
+
 // StereoReprojectionError (BundleAdjuster.h:153-171): residual, optional J
-__device__ __forceinline__ void stereo_residual(const Geo& g, const double* cam, const double* X, const double* f,
-                                                double* r, double* Jc, double* Jp) {
+template <bool TAB>
+__device__ __forceinline__ void stereo_residual(const Geo& g, const double* cam, const double* rot, const double* X,
+                                                const double* f, double* r, double* Jc, double* Jp) {
   double P[3], dPdw[9], dPdX[9];
-  rotate(cam + 3, X, P, Jc ? dPdw : nullptr, Jc ? dPdX : nullptr);
+  rotate_cam<TAB>(cam, rot, X, P, Jc ? dPdw : nullptr, Jc ? dPdX : nullptr);
   P[0] = P[0] + cam[0];
   P[1] = P[1] + cam[1];
   P[2] = P[2] + cam[2];
@@ -203,10 +288,11 @@ __device__ __forceinline__ void stereo_residual(const Geo& g, const double* cam,
 // for camID 0, StereoRightError (:106-139, p.x += cam[0] - baseline) otherwise;
 // both project with K[0].  Rows 2, 3 are zero so the 4-row pipeline is shared
 // (zero rows add nothing to J^T J, J^T r or the Huber argument).
-__device__ __forceinline__ void mono_residual(const Geo& g, const double* cam, const double* X, const double* f,
-                                              bool right, double* r, double* Jc, double* Jp) {
+template <bool TAB>
+__device__ __forceinline__ void mono_residual(const Geo& g, const double* cam, const double* rot, const double* X,
+                                              const double* f, bool right, double* r, double* Jc, double* Jp) {
   double P[3], dPdw[9], dPdX[9];
-  rotate(cam + 3, X, P, Jc ? dPdw : nullptr, Jc ? dPdX : nullptr);
+  rotate_cam<TAB>(cam, rot, X, P, Jc ? dPdw : nullptr, Jc ? dPdX : nullptr);
   P[0] = P[0] + (right ? cam[0] - g.baseline : cam[0]);
   P[1] = P[1] + cam[1];
   P[2] = P[2] + cam[2];
@@ -237,9 +323,22 @@ template <int OD>
 __device__ __forceinline__ void obs_residual(const Geo& g, const Bufs& b, long o, const double* cam, const double* X,
                                              double* r, double* Jc, double* Jp) {
   if (OD == 4)
-    stereo_residual(g, cam, X, b.obs + 4 * o, r, Jc, Jp);
+    stereo_residual<false>(g, cam, nullptr, X, b.obs + 4 * o, r, Jc, Jp);
   else
-    mono_residual(g, cam, X, b.obs + 2 * o, b.cam_id[o] != 0, r, Jc, Jp);
+    mono_residual<false>(g, cam, nullptr, X, b.obs + 2 * o, b.cam_id[o] != 0, r, Jc, Jp);
+}
+// The table form: the rotation terms from the camera's entry `rot` of Bufs::rot
+// (cam gives the translation).  The linearisation (lin_pieces) and the camera
+// assembly use this one; the cost, evaluation and covariance entry points keep
+// rotate()'s per-observation form above.
+template <int OD>
+__device__ __forceinline__ void obs_residual_tab(const Geo& g, const Bufs& b, long o, const double* cam,
+                                                 const double* rot, const double* X, double* r, double* Jc,
+                                                 double* Jp) {
+  if (OD == 4)
+    stereo_residual<true>(g, cam, rot, X, b.obs + 4 * o, r, Jc, Jp);
+  else
+    mono_residual<true>(g, cam, rot, X, b.obs + 2 * o, b.cam_id[o] != 0, r, Jc, Jp);
 }
 
 // ceres::HuberLoss(1.0): rho0 and sqrt(rho1) (Corrector with rho'' <= 0)
@@ -296,10 +395,10 @@ __host__ __device__ inline int lin_block(int no) { return no <= kLinSmallMaxObs 
 // observation's cost 0.5 rho0.  The one definition behind linearize_kernel and
 // the fused phase A of pt_schur_kernel: the same expressions, the same bits.
 template <int OD>
-__device__ __forceinline__ double lin_pieces(const Geo& g, const Bufs& b, long o, const double* cam, const double* pt,
-                                             bool var, double* X, double* W) {
+__device__ __forceinline__ double lin_pieces(const Geo& g, const Bufs& b, long o, const double* cam, const double* rot,
+                                             const double* pt, bool var, double* X, double* W) {
   double r[4], Jc[24], Jp[12];
-  obs_residual<OD>(g, b, o, cam, pt, r, Jc, Jp);
+  obs_residual_tab<OD>(g, b, o, cam, rot, pt, r, Jc, Jp);
   const double s = r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3];
   double rho0, sc;
   huber(s, &rho0, &sc);
@@ -336,7 +435,7 @@ __global__ __launch_bounds__(BLK) void linearize_kernel(Geo g, Bufs b) {
     const int ci = b.cam_idx[o], pi = b.pt_idx[o];
     const long slot = b.pos[o];  // CSR-by-point slot: per-point stages read contiguously
     // (the pieces go straight to their slot of obsx / Wo)
-    cost = lin_pieces<OD>(g, b, o, b.cams[cur] + 6 * ci, b.pts[cur] + 3 * pi, ci - g.nf >= 0,
+    cost = lin_pieces<OD>(g, b, o, b.cams[cur] + 6 * ci, b.rot[cur] + kRotStride * ci, b.pts[cur] + 3 * pi, ci - g.nf >= 0,
                           b.obsx + slot * kObsxStride, b.Wo + 18 * slot);
   }
   double v[1] = {cost};
@@ -464,9 +563,11 @@ __device__ __forceinline__ void cam_assemble_body(const Geo& g, const Bufs& b, d
     // linearize_kernel forms them (same function, same Huber scaling: the same
     // pieces bit for bit), then Jc^T Jc (21) and Jc^T r (6)
     const int o = b.c_obs[q];
-    const int cam = b.cam_idx[o], pi = b.pt_idx[o];
+    // (the unit's camera: variable camera ci of the window, the same for every
+    // slot of the unit, so its parameters and table entry load once per wave)
+    const int cam = ci + g.nf, pi = b.pt_idx[o];
     double r[4], Jc[24], Jp[12];
-    obs_residual<OD>(g, b, o, b.cams[cur] + 6 * cam, b.pts[cur] + 3 * pi, r, Jc, Jp);
+    obs_residual_tab<OD>(g, b, o, b.cams[cur] + 6 * cam, b.rot[cur] + kRotStride * cam, b.pts[cur] + 3 * pi, r, Jc, Jp);
     const double s2 = r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3];
     double rho0, sc;
     huber(s2, &rho0, &sc);
@@ -799,7 +900,8 @@ __global__ __launch_bounds__(BLK) void pt_schur_kernel(Geo g, Bufs b, Opts o, Ca
           double xl[3], w[18];
           for (int a = 0; a < 3; ++a) xl[a] = b.pts[cur][3 * (long)j + a];
           const bool var = ci >= 0 && !final_pass;  // (no W_o for a fixed camera, nor for the closing pass)
-          cost += lin_pieces<OD>(g, b, ob, b.cams[cur] + 6 * (ci + g.nf), xl, var, X, w);
+          cost += lin_pieces<OD>(g, b, ob, b.cams[cur] + 6 * (ci + g.nf), b.rot[cur] + kRotStride * (ci + g.nf), xl, var,
+                                 X, w);
           if (var)
             for (int i = 0; i < 18; ++i) b.Wo[18 * (long)q + i] = w[i];
           k = (q - beg) / SL;
@@ -2637,7 +2739,36 @@ __device__ void cam_step_body(const Geo& g, const Bufs& b, int cur, double* lds)
   }
 }
 
-// Grid: g.nblk_step point workgroups + the camera workgroup (cam_step_body).
+// The candidates' rotation table, rot[1 - cur] beside cams[1 - cur], which the
+// next launches read if the step is accepted (a rejected step leaves cur and
+// rot[cur] alone).  The thread of camera c forms the candidate rotation itself
+// (cam_cand: the bits cam_step_body stored), so it waits for no store; a fixed
+// camera's entry is copied.  The camera workgroup runs this AFTER its arrival
+// (pt_step_kernel), with the `cur` it read before: the chain (sqrt, sin, cos,
+// ten divisions) then runs beside the point workgroups still at work and the
+// finalizing workgroup, which read neither table, and nothing it reads
+// (cams[cur], csc, yc) is written by them.  Ahead of the arrival it lengthened
+// the launch by 0.5 us (profiles/rot_tables_kernel_stats.txt).
+__device__ void rot_step_body(const Geo& g, const Bufs& b, int cur) {
+  const double* x = b.cams[cur];
+  const double* rx = b.rot[cur];
+  double* rc = b.rot[1 - cur];
+  for (int c = threadIdx.x; c < g.nc; c += blockDim.x) {
+    if (c < g.nf) {
+      for (int k = 0; k < kRotStride; ++k) rc[kRotStride * c + k] = rx[kRotStride * c + k];
+      continue;
+    }
+    double aa[3];
+    for (int a = 0; a < 3; ++a) {
+      const int i = 6 * (c - g.nf) + 3 + a;
+      aa[a] = cam_cand(x[6 * c + 3 + a], b.csc[i] * b.yc[i]);
+    }
+    rot_entry(aa, rc + kRotStride * c);
+  }
+}
+
+// Grid: g.nblk_step point workgroups + the camera workgroup (cam_step_body,
+// then rot_step_body behind its arrival).
 template <int OD>
 __global__ __launch_bounds__(kStepBlock) void pt_step_kernel(Geo g, Bufs b, Opts o, int do_decide) {
   __shared__ double lds[16];
@@ -2649,10 +2780,14 @@ __global__ __launch_bounds__(kStepBlock) void pt_step_kernel(Geo g, Bufs b, Opts
 #ifdef ME_STEP_TS
   long long step_prev_ = 0, fin_prev_ = 0;
 #endif
+  // (the camera workgroup: a failed solve wrote no step, so no candidate and no
+  // table; read here, before the arrival -- the finalizing workgroup's decide
+  // flips cur and clears fail)
+  const bool cam_wg = (int)blockIdx.x == g.nblk_step && !st->fail;
+  const int cam_cur = st->cur;
   if ((int)blockIdx.x == g.nblk_step) {
-    // (a failed solve wrote no step; thread 0's scalar stores drain before its
-    // arrival, last_arrival_wt)
-    if (!st->fail) cam_step_body(g, b, st->cur, lds);
+    // (thread 0's scalar stores drain before its arrival, last_arrival_wt)
+    if (cam_wg) cam_step_body(g, b, cam_cur, lds);
   } else {
   STEP_T(0);
   const int gl = threadIdx.x & (kStepG - 1);
@@ -2812,9 +2947,9 @@ __global__ __launch_bounds__(kStepBlock) void pt_step_kernel(Geo g, Bufs b, Opts
       }
       double r[4];
       if (OD == 4)
-        stereo_residual(g, cv, xc, f, r, nullptr, nullptr);
+        stereo_residual<false>(g, cv, nullptr, xc, f, r, nullptr, nullptr);
       else
-        mono_residual(g, cv, xc, f, right, r, nullptr, nullptr);
+        mono_residual<false>(g, cv, nullptr, xc, f, right, r, nullptr, nullptr);
       const double s = r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3];
       double rho0, sc;
       huber(s, &rho0, &sc);
@@ -2834,7 +2969,10 @@ __global__ __launch_bounds__(kStepBlock) void pt_step_kernel(Geo g, Bufs b, Opts
   }  // (point workgroups)
   // the last workgroup to finish (of either kind) reduces the partials
   // (step_finalize) and, single-GPU, runs the Ceres step handling
-  if (!last_arrival_wt(b.cnt + g.m, gridDim.x)) return;
+  if (!last_arrival_wt(b.cnt + g.m, gridDim.x)) {
+    if (cam_wg) rot_step_body(g, b, cam_cur);
+    return;
+  }
 #ifdef ME_STEP_TS
   if (threadIdx.x == 0) fin_prev_ = (long long)__builtin_amdgcn_s_memtime();
 #endif
@@ -2843,6 +2981,7 @@ __global__ __launch_bounds__(kStepBlock) void pt_step_kernel(Geo g, Bufs b, Opts
 #ifdef ME_STEP_TS
   if (threadIdx.x == 0) atomicAdd(&g_step_ts[7], 1ull);
 #endif
+  if (cam_wg) rot_step_body(g, b, cam_cur);  // (the camera workgroup arrived last: the table behind the step's decision)
 }
 
 __global__ void decide_kernel(Geo g, Bufs b, Opts o) {
@@ -2986,6 +3125,12 @@ __global__ __launch_bounds__(kBlock) void plan_count_kernel(Geo g, Bufs b, const
   const PlanWork w = plan_work(g, b.work);
   const int t = threadIdx.x, blk = blockIdx.x;
   const long gid = (long)blk * kBlock + t;
+  // the launch's last workgroup: the starting cameras' rotation table, beside
+  // the counting workgroups (its sin / cos chain on none of their paths)
+  if (blk == (int)gridDim.x - 1) {
+    for (int c = t; c < g.nc; c += kBlock) rot_entry(cams_in + 6 * c + 3, b.rot[0] + kRotStride * c);
+    return;
+  }
   for (int c = t; c < g.nc; c += kBlock) lcnt[c] = 0;
   __syncthreads();
   if (blk < g.nblk_obs && gid < g.no) {
@@ -3594,6 +3739,10 @@ int plan_build(me_ctx* c, const me_ba_problem* p, const me_ba_options* opt, Plan
   add(8 * out_doubles, &b.out);
   b.xch = nullptr;
   if (comm) add(8 * (size_t)xo_total(g), &b.xch);
+  // the rotation tables last: every other buffer keeps the offset it had without them (ahead of cams[1] the
+  // config-5 solve measured 1.3 % behind the parent commit's, profiles/rot_tables_ab.txt)
+  add(8 * kRotStride * (size_t)g.nc, &b.rot[0]);
+  add(8 * kRotStride * (size_t)g.nc, &b.rot[1]);
   size_t total = 0, input_span = 0;
   for (size_t k = 0; k < items.size(); ++k) {
     total += items[k].first;
@@ -3655,8 +3804,8 @@ int plan_build(me_ctx* c, const me_ba_problem* p, const me_ba_options* opt, Plan
   const double* cams_in = dev ? p->cams : b.cams[0];
   const double* pts_in = dev ? p->pts : b.pts[0];
   const long nthr = std::max({(long)g.nblk_obs * kBlock, (long)g.np, 6L * g.nc, 3L * g.np});
-  hipLaunchKernelGGL(plan_count_kernel, dim3(blocks(nthr, kBlock)), dim3(kBlock), 4 * (size_t)g.nc, s, g, b, cams_in,
-                     pts_in);
+  hipLaunchKernelGGL(plan_count_kernel, dim3(blocks(nthr, kBlock) + 1), dim3(kBlock), 4 * (size_t)g.nc, s, g, b,
+                     cams_in, pts_in);  // (+ 1: the rotation table's workgroup)
   hipLaunchKernelGGL(plan_scan_kernel, dim3(1), dim3(kScanBlock), 0, s, g, b, o);
   hipLaunchKernelGGL(plan_scatter_kernel, dim3(g.nblk_obs), dim3(kBlock), 0, s, g, b);
   hipLaunchKernelGGL(plan_segsort_kernel, dim3(blocks(std::max(g.np, 1), kSortBlock / 64)), dim3(kSortBlock), 0, s, g,

@@ -92,6 +92,7 @@ struct Geo {
 struct Bufs {
   double* cams[2];
   double* pts[2];
+  double* rot[2];     // per camera (fixed ones included) the rotation table entry of cams[k], kRotStride doubles: see below
   const double* obs;
   const int* cam_idx;
   const int* pt_idx;
@@ -141,6 +142,17 @@ struct Bufs {
   double* out;        // State | cams[cur] | pts[cur] for the single read-back
   double* xch;        // sharded only (else null): the packed per-iteration exchange, see xo_* below
 };
+
+// Rotation table (rot[k] beside cams[k], indexed by State::cur alike): what an
+// observation's residual and Jacobian need of its camera's angle-axis vector,
+// built once per camera where the cameras are written (the plan's first
+// launch; the camera workgroup of pt_step for the candidates) and read by the
+// linearisation and the camera assembly of the next launches.  Per camera:
+// R (9, row-major) | M = (w w^T + (R^T - I)[w]x) / theta^2 (9, divided) | the
+// branch word: 1.0 for theta^2 > DBL_EPSILON, else 0.0 -- the small-angle form
+// P = X + w x X, where R holds I + [w]x and M is unused | one word of padding.
+constexpr int kRotStride = 20;
+enum { ROT_R = 0, ROT_M = 9, ROT_BRANCH = 18 };
 
 // Camera-assembly unit table: a unit is 256 consecutive slots of one variable
 // camera's segment of c_obs; camera c has max(1, ceil(n_c / 256)) units (an
