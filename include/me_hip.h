@@ -733,7 +733,25 @@ int me_ba_solve_sharded(me_ctx* ctx, me_ba_problem* p, const me_ba_options* o, m
 int me_ba_shard_worthwhile(long n_obs, int world, double xch_us);
 double me_ba_shard_exchange_us(int world);
 
-/* ---- A12: KLT feature tracking (build-defined; no reference) ---------- */
+/* ---- A12: KLT feature tracking (build-defined; no reference) ----------
+ * The position contract.  At pyramid level L (scale sc = 2^-L, exact) the
+ * template window of feature p has the float32 origin xw = p.x * sc -
+ * (win - 1) / 2, yw likewise, and lies inside the level iff
+ *     xw >= 0 && xw < W_L - win && yw >= 0 && yw < H_L - win,
+ * compared as floats, before anything is converted to an integer: the same
+ * predicate as 0 <= floor(xw), floor(xw) + win < W_L for every position whose
+ * floor fits an int, false for NaN and "outside" for +-inf and for positions
+ * of any magnitude.  The search window of every iteration is tested the same
+ * way.  A level whose template window is outside is skipped.  A feature whose
+ * position is NaN or +-inf in either component, or whose template window is
+ * outside at level 0, is never read from the images and gets status 0; its
+ * pts_out is what the level loop leaves, per component: p * 2^-max_level
+ * doubled max_level times when every level skipped it (p itself, bit for bit,
+ * unless the scaling underflowed; NaN for a NaN input: compare with isnan, the
+ * payload is not specified), otherwise where the upper levels' searches
+ * arrived, scaled to level 0.  The other features of a call are unaffected.
+ * me_klt_track_fb and the guided forms inherit the rule for pts_in; their own
+ * extra inputs (the gate's start, the guess) are tested in float as well. */
 typedef struct { int win; int max_level; int max_iters; double eps; double min_eig; } me_klt_params;
 void me_klt_default_params(me_klt_params* p);
 int me_klt_track(me_ctx* ctx, me_mem mem, const uint8_t* prev, const uint8_t* next, int width, int height,

@@ -23,6 +23,15 @@ inline int refl(int i, int n) {
   while (i < 0 || i >= n) { if (i < 0) i = -i; if (i >= n) i = 2 * n - 2 - i; }
   return i;
 }
+// The win x win window (plus its bilinear neighbours) with origin (floor(xw),
+// floor(yw)) lies inside a level: 0 <= floor(xw), floor(xw) + win < w and the
+// same in y, asked of the floats (xmax = w - win, ymax = h - win; the same
+// predicate for every floor that fits an int).  False for NaN, +-inf and
+// positions past the int range, whose (int) cast would be undefined: the
+// origin is converted only after this test (me_hip.h A12, position contract).
+inline bool win_inside(float xw, float yw, int xmax, int ymax) {
+  return xw >= 0.f && xw < (float)xmax && yw >= 0.f && yw < (float)ymax;
+}
 inline int descale(long v, int n) { return (int)((v + (1L << (n - 1))) >> n); }
 
 struct Level { int w, h; std::vector<uint8_t> I; std::vector<int16_t> dx, dy; };
@@ -94,8 +103,8 @@ extern "C" void oracle_klt_track(const uint8_t* prev, const uint8_t* next, int w
       if (L == kp->max_level) { nx = px; ny = py; }
       else { nx = nx * 2.0f; ny = ny * 2.0f; }
       float pxw = px - (float)half, pyw = py - (float)half;
+      if (!win_inside(pxw, pyw, lp.w - win, lp.h - win)) { if (L == 0) st = 0; continue; }
       int ix0 = (int)std::floor(pxw), iy0 = (int)std::floor(pyw);
-      if (ix0 < 0 || iy0 < 0 || ix0 + win >= lp.w || iy0 + win >= lp.h) { if (L == 0) st = 0; continue; }
       float a = pxw - (float)ix0, b = pyw - (float)iy0;
       int iw00 = (int)std::rint((1.f - a) * (1.f - b) * 16384.f);
       int iw01 = (int)std::rint(a * (1.f - b) * 16384.f);
@@ -120,8 +129,8 @@ extern "C" void oracle_klt_track(const uint8_t* prev, const uint8_t* next, int w
       float nxw = nx - (float)half, nyw = ny - (float)half;
       float pdx = 0, pdy = 0;
       for (int j = 0; j < kp->max_iters; ++j) {
+        if (!win_inside(nxw, nyw, ln.w - win, ln.h - win)) { if (L == 0) st = 0; break; }
         int jx0 = (int)std::floor(nxw), jy0 = (int)std::floor(nyw);
-        if (jx0 < 0 || jy0 < 0 || jx0 + win >= ln.w || jy0 + win >= ln.h) { if (L == 0) st = 0; break; }
         float c = nxw - (float)jx0, d = nyw - (float)jy0;
         int jw00 = (int)std::rint((1.f - c) * (1.f - d) * 16384.f);
         int jw01 = (int)std::rint(c * (1.f - d) * 16384.f);

@@ -112,6 +112,37 @@ int main() {
   }
   oracle_klt_track(L.data(), L2.data(), W, H, W, pin.data(), pout.data(), st.data(), nf, &kp);
   for (int k = 0; k < nf; ++k) chk += st[k] ? pout[2 * k] : 0.0;
+  {  // positions that are not finite, past the int range or on the image's edge (me_hip.h A12, the position
+    // contract): status 0, nothing converted or read out of range, the valid rows between them untouched
+    const float inf = INFINITY, nan = NAN, x = 40.37f, y = 50.37f;
+    const float bad[][2] = {{nan, y}, {x, nan}, {nan, nan}, {inf, y}, {x, -inf}, {2147483648.0f, y}, {3e9f, 3e9f},
+                            {1e30f, 1e30f}, {-1e30f, y}, {-0.0f, -0.0f}, {(float)(W - 1), (float)(H - 1)},
+                            {std::nextafter((float)W, inf), y}, {-inf, inf}, {-2147483648.0f, -2147483904.0f}};
+    const int nb = (int)(sizeof bad / sizeof bad[0]), nn = 2 * nb;
+    std::vector<float> qin(2 * nn), qout(2 * nn);
+    std::vector<uint8_t> qst(nn);
+    for (int k = 0; k < nb; ++k) {
+      qin[4 * k] = bad[k][0];
+      qin[4 * k + 1] = bad[k][1];
+      qin[4 * k + 2] = pin[2 * k];  // a valid row after every bad one
+      qin[4 * k + 3] = pin[2 * k + 1];
+    }
+    for (int lv : {3, 0}) {
+      oracle_klt_params kq{21, lv, 30, 0.01, 1e-4};
+      oracle_klt_track(L.data(), L2.data(), W, H, W, qin.data(), qout.data(), qst.data(), nn, &kq);
+      for (int k = 0; k < nb; ++k) {
+        if (qst[2 * k] != 0) {
+          std::printf("sanitize_driver: KLT row %d (%g, %g) got status 1\n", k, bad[k][0], bad[k][1]);
+          return 1;
+        }
+        if (lv == 3 && (qst[2 * k + 1] != st[k] || std::memcmp(&qout[4 * k + 2], &pout[2 * k], 8) != 0)) {
+          std::printf("sanitize_driver: KLT valid row %d moved beside a bad one\n", k);
+          return 1;
+        }
+        chk += qst[2 * k + 1] ? qout[4 * k + 2] : 0.0;
+      }
+    }
+  }
 
   // A13-A17 BA: 6 cameras moving forward, 80 points, tracks of >= 2 frames
   const int nc = 6, np = 80;

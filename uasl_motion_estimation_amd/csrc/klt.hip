@@ -223,6 +223,15 @@ __device__ __forceinline__ void stage_region(uint32_t* reg, const uint8_t* __res
   wave_lds_sync();
 }
 
+// 0 <= floor(xw), floor(xw) + win < W and the same in y, asked of the floats:
+// xmax = W - win, ymax = H - win.  Every comparison is false for NaN; +-inf
+// and values whose floor would not fit an int are outside.  Every lane holds
+// the same position; the ballot makes the answer a scalar condition.
+__device__ __forceinline__ bool win_inside(float xw, float yw, int xmax, int ymax) {
+  const bool in = xw >= 0.f && xw < (float)xmax && yw >= 0.f && yw < (float)ymax;
+  return __builtin_amdgcn_ballot_w64(in) != 0ull;
+}
+
 // Every lane loads all of its window pixels unconditionally (pixels past the
 // window alias pixel 0 and are masked afterwards), so the loads of one step
 // issue back to back behind a single wait instead of one round trip per pixel.
@@ -301,13 +310,19 @@ __global__ __launch_bounds__(256) void klt_kernel(Pyr P, const float* __restrict
       ny = ny * 2.0f;
     }
     const float pxw = px - (float)half, pyw = py - (float)half;
-    int iv0[2] = {(int)floorf(pxw), (int)floorf(pyw)};
-    asm volatile("" : "+v"(iv0[0]), "+v"(iv0[1]));
-    const int ix0 = __builtin_amdgcn_readfirstlane(iv0[0]), iy0 = __builtin_amdgcn_readfirstlane(iv0[1]);
-    if (ix0 < 0 || iy0 < 0 || ix0 + win >= W || iy0 + win >= H) {
+    // "window inside the level" is decided on the floats and the origin is
+    // converted only afterwards (me_hip.h A12, the position contract): for a
+    // floor that fits an int, floor(p) >= 0 <=> p >= 0 and floor(p) + win >= W
+    // <=> p >= W - win (an integer), the test on the converted origin; NaN,
+    // +-inf and positions past the int range compare false (v_cvt_i32_f32
+    // gives 0 for NaN and saturates, and INT_MAX + win wraps to "inside")
+    if (!win_inside(pxw, pyw, W - win, H - win)) {
       if (L == 0) st = 0;
       continue;
     }
+    int iv0[2] = {(int)floorf(pxw), (int)floorf(pyw)};
+    asm volatile("" : "+v"(iv0[0]), "+v"(iv0[1]));
+    const int ix0 = __builtin_amdgcn_readfirstlane(iv0[0]), iy0 = __builtin_amdgcn_readfirstlane(iv0[1]);
     const float a = pxw - (float)ix0, b = pyw - (float)iy0;
     const int iw00 = (int)rintf((1.f - a) * (1.f - b) * 16384.f);
     const int iw01 = (int)rintf(a * (1.f - b) * 16384.f);
@@ -382,12 +397,12 @@ __global__ __launch_bounds__(256) void klt_kernel(Pyr P, const float* __restrict
     for (int j = 0; j < max_iters; ++j) {
       // (the position, its weights and the region test are wave-uniform -- every
       // lane runs the same arithmetic on the same values: scalar registers)
-      const int jx0 = __builtin_amdgcn_readfirstlane((int)floorf(nxw));
-      const int jy0 = __builtin_amdgcn_readfirstlane((int)floorf(nyw));
-      if (jx0 < 0 || jy0 < 0 || jx0 + win >= W || jy0 + win >= H) {
+      if (!win_inside(nxw, nyw, W - win, H - win)) {  // (on the floats, as for the template)
         if (L == 0) st = 0;
         break;
       }
+      const int jx0 = __builtin_amdgcn_readfirstlane((int)floorf(nxw));
+      const int jy0 = __builtin_amdgcn_readfirstlane((int)floorf(nyw));
       const float c = nxw - (float)jx0, d = nyw - (float)jy0;
       // (converted in a vector register, then read once into a scalar one: the
       // weight packing below runs on the scalar unit)

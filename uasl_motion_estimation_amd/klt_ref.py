@@ -111,8 +111,30 @@ def _bilinear(flat, w, x0, y0, wts, oy, ox):
     return flat[o] * w00 + flat[o + 1] * w01 + flat[o + w] * w10 + flat[o + w + 1] * w11
 
 
-def klt_track_ref(prev, next, pts, guess=None, win=21, max_level=3, max_iters=30, eps=0.01, min_eig=1e-4):
-    """me_klt_track (guess None) / me_klt_track_guided: (pts_out (n, 2) float32, status (n,) uint8)."""
+TRACE_COUNTS = ("reject_l0", "reject_upper", "left_image", "iters", "iters_w11_neg", "templates_w11_neg",
+                "oscillation", "exhausted")
+TRACE_MAXIMA = ("max_a11", "max_abs_a12", "max_a22", "max_abs_b1", "max_abs_b2")
+
+
+def _trace_add(trace, key, v):
+    trace[key] = trace.get(key, 0) + int(v)
+
+
+def _trace_max(trace, key, a):
+    trace[key] = max(trace.get(key, 0), int(np.abs(a).max()) if len(a) else 0)
+
+
+def klt_track_ref(prev, next, pts, guess=None, win=21, max_level=3, max_iters=30, eps=0.01, min_eig=1e-4,
+                  trace: dict | None = None):
+    """me_klt_track (guess None) / me_klt_track_guided: (pts_out (n, 2) float32, status (n,) uint8).
+
+    trace: a dict that accumulates, over the calls it is passed to, which paths the features took (the tests
+    prove from it that an input reaches the path it is named for).  Per (feature, level): "outside" {level:
+    templates skipped because their window was outside}, "reject_l0" / "reject_upper" (minimum eigenvalue or
+    determinant, level 0 / levels above), "left_image" (search window left the level), "oscillation" (the
+    half-step exit), "exhausted" (ran all max_iters iterations), "templates_w11_neg" (fourth template weight
+    -1).  "iters" / "iters_w11_neg": iterations run / with the fourth weight -1.  "max_a11", "max_abs_a12",
+    "max_a22", "max_abs_b1", "max_abs_b2": the largest window sums seen, integers before FLT_SCALE."""
     prev = np.ascontiguousarray(prev, np.uint8)
     nxt = np.ascontiguousarray(next, np.uint8)
     if prev.shape != nxt.shape or prev.ndim != 2:
@@ -123,6 +145,10 @@ def klt_track_ref(prev, next, pts, guess=None, win=21, max_level=3, max_iters=30
     start = start_points(pts, guess, W0, H0)
     st = np.ones(n, np.uint8)
     nx, ny = np.zeros(n, F32), np.zeros(n, F32)
+    if trace is not None:
+        trace.setdefault("outside", {})
+        for key in TRACE_COUNTS + TRACE_MAXIMA:
+            trace.setdefault(key, 0)
     if n == 0:
         return np.zeros((0, 2), F32), st
     P, N = pyramid(prev, max_level), pyramid(nxt, max_level)
@@ -149,21 +175,32 @@ def klt_track_ref(prev, next, pts, guess=None, win=21, max_level=3, max_iters=30
         if L == 0:
             st[~inside] = 0
         k = np.flatnonzero(inside)
+        if trace is not None:
+            trace["outside"][L] = trace["outside"].get(L, 0) + int(n - len(k))
         if len(k) == 0:
             continue
         x0, y0 = ix0[k], iy0[k]
         wts = _weights(pxw[k] - x0.astype(F32), pyw[k] - y0.astype(F32))
+        if trace is not None:
+            _trace_add(trace, "templates_w11_neg", (wts[3] < 0).sum())
         iv = _descale(_bilinear(If, W, x0, y0, wts, oy, ox), 9)
         gx = _descale(_bilinear(Dxf, W, x0, y0, wts, oy, ox), 14)
         gy = _descale(_bilinear(Dyf, W, x0, y0, wts, oy, ox), 14)
-        a11 = (gx * gx).sum(1).astype(np.float64) * FLT_SCALE
-        a12 = (gx * gy).sum(1).astype(np.float64) * FLT_SCALE
-        a22 = (gy * gy).sum(1).astype(np.float64) * FLT_SCALE
+        A11, A12, A22 = (gx * gx).sum(1), (gx * gy).sum(1), (gy * gy).sum(1)
+        if trace is not None:
+            _trace_max(trace, "max_a11", A11)
+            _trace_max(trace, "max_abs_a12", A12)
+            _trace_max(trace, "max_a22", A22)
+        a11 = A11.astype(np.float64) * FLT_SCALE
+        a12 = A12.astype(np.float64) * FLT_SCALE
+        a22 = A22.astype(np.float64) * FLT_SCALE
         D = a11 * a22 - a12 * a12
         min_e = (a22 + a11 - np.sqrt((a11 - a22) * (a11 - a22) + 4.0 * a12 * a12)) / (2.0 * win * win)
         good = ~((min_e < min_eig) | (D < 1.1920928955078125e-07))
         if L == 0:
             st[k[~good]] = 0
+        if trace is not None:
+            _trace_add(trace, "reject_l0" if L == 0 else "reject_upper", (~good).sum())
         k, iv, gx, gy = k[good], iv[good], gx[good], gy[good]
         a11, a12, a22, D = a11[good], a12[good], a22[good], D[good]
         if len(k) == 0:
@@ -182,13 +219,21 @@ def klt_track_ref(prev, next, pts, guess=None, win=21, max_level=3, max_iters=30
             if L == 0:
                 st[k[r[~ins]]] = 0
             run[r[~ins]] = False
+            if trace is not None:
+                _trace_add(trace, "left_image", (~ins).sum())
             r, jx0, jy0 = r[ins], jx0[ins], jy0[ins]
             if len(r) == 0:
                 break
             wj = _weights(nxw[r] - jx0.astype(F32), nyw[r] - jy0.astype(F32))
             diff = _descale(_bilinear(Jf, W, jx0, jy0, wj, oy, ox), 9) - iv[r]
-            b1d = (diff * gx[r]).sum(1).astype(np.float64) * FLT_SCALE
-            b2d = (diff * gy[r]).sum(1).astype(np.float64) * FLT_SCALE
+            B1, B2 = (diff * gx[r]).sum(1), (diff * gy[r]).sum(1)
+            if trace is not None:
+                _trace_add(trace, "iters", len(r))
+                _trace_add(trace, "iters_w11_neg", (wj[3] < 0).sum())
+                _trace_max(trace, "max_abs_b1", B1)
+                _trace_max(trace, "max_abs_b2", B2)
+            b1d = B1.astype(np.float64) * FLT_SCALE
+            b2d = B2.astype(np.float64) * FLT_SCALE
             with np.errstate(invalid="ignore", over="ignore"):
                 ddx = ((a12[r] * b2d - a22[r] * b1d) * Dinv[r]).astype(F32)
                 ddy = ((a12[r] * b1d - a11[r] * b2d) * Dinv[r]).astype(F32)
@@ -206,6 +251,10 @@ def klt_track_ref(prev, next, pts, guess=None, win=21, max_level=3, max_iters=30
                     ny[kb] = ny[kb] - ddy[back] * F32(0.5)
             run[r[small | back]] = False
             pdx[r], pdy[r] = ddx, ddy
+            if trace is not None:
+                _trace_add(trace, "oscillation", back.sum())
+        if trace is not None:
+            _trace_add(trace, "exhausted", run.sum())
     return np.stack([nx, ny], -1).astype(F32), st
 
 
