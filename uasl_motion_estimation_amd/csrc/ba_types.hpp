@@ -1,5 +1,6 @@
-// ba_kernels.hpp — device kernels of the windowed stereo bundle adjuster
-// (SURVEY §8a A13-A17).  Included by ba.hip only.
+// ba_types.hpp — the types, buffer layouts and kernel map of the windowed
+// stereo bundle adjuster; no kernel.  Included by ba.hip
+// and its per-stage parts (ba_*.hpp) only.
 //
 // Replaces the Ceres solve behind BundleAdjuster<4>::optimise
 // (include/MotionEstimation/optimisation/BundleAdjuster.h:431-476) and

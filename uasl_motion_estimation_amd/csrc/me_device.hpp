@@ -12,7 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-// Cross-workgroup hand-offs inside one launch (ba.hip: last_arrival_wt, the
+// Cross-workgroup hand-offs inside one launch (ba_reduce.hpp: last_arrival_wt; the
 // fused assembly, the multi-workgroup camera solve; scale.hip:
 // last_block_arrives, wt_store): the producer stores with agent-scope
 // atomics (written through, sc1), every storing wave drains (s_waitcnt

@@ -1,6 +1,6 @@
 // roster.hpp — co-residency without assumptions, for the launches whose
 // workgroups wait on one another: the persistent scale LM grid (scale.hip
-// scale_lm_kernel), the camera solve's trailing-update workers (ba.hip
+// scale_lm_kernel), the camera solve's trailing-update workers (ba_cam_solve.hpp
 // cam_solve_kernel<2>) and its fused Schur assemblers (cam_solve_kernel<0/1>).
 //
 // A plain launch does not promise that all of its workgroups are resident at

@@ -1,4 +1,4 @@
-// solve_diag.hpp -- the camera solve's diagonal-block factorisation (ba.hip),
+// solve_diag.hpp -- the camera solve's diagonal-block factorisation (ba_cam_solve.hpp),
 // kept in a header so tools/ubench/diag.hip times the same code in isolation.
 #pragma once
 #include <hip/hip_runtime.h>

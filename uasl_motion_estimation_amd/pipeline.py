@@ -64,7 +64,7 @@ def R_to_quat(R):
     return S.R_to_quat(R)
 
 
-# (-1)^k / (2k+1)! and (-1)^k / (2k+2)!: the same literals as vo_chain_kernel (csrc/ba.hip)
+# (-1)^k / (2k+1)! and (-1)^k / (2k+2)!: the same literals as vo_chain_kernel (csrc/ba_vo_chain.hpp)
 _ROT_A = (1.0, -0.16666666666666666, 0.008333333333333333, -0.0001984126984126984, 2.7557319223985893e-06,
           -2.505210838544172e-08, 1.6059043836821613e-10, -7.647163731819816e-13, 2.8114572543455206e-15,
           -8.22063524662433e-18, 1.9572941063391263e-20, -3.868170170630684e-23, 6.446950284384474e-26,
