@@ -343,12 +343,23 @@ typedef struct {
   int successful_steps;
   double initial_cost, final_cost;
 } me_ba_summary;
+/* final_cost.  With gradient_tolerance > 0 (or max_num_iterations == 0) a solve
+   that reaches the iteration limit linearises once more at its final point for
+   the closing gradient test, and final_cost is that linearisation's cost.  With
+   gradient_tolerance <= 0 and max_num_iterations > 0 that pass is not run: the
+   last step's decision ends the solve, and final_cost is the candidate cost of
+   the last accepted step -- the same quantity, summed from the step
+   evaluation's residuals, not the linearisation's (equal to about 1e-13
+   relative).  A final point whose gradient is exactly zero in every component
+   then reports the iteration limit (termination 1), not convergence: with the
+   tolerance at 0 only such a gradient could pass the closing test. */
 
 void me_ba_default_options(me_ba_options* o);
 int me_ba_solve(me_ctx* ctx, me_ba_problem* p, const me_ba_options* o, me_ba_summary* s);
 /* Asynchronous form of me_ba_solve (same BundleAdjuster<M>::optimise,
    BundleAdjuster.h:378-476, same results bit for bit): queues every
-   possible iteration (max_num_iterations + 1 linearisations; launches after
+   possible iteration (max_num_iterations linearisations, one more where the
+   closing gradient test runs, see me_ba_summary; launches after
    convergence return at once, so it suits fixed-iteration windows) and the
    read-back on the ctx stream, and returns without waiting.  The caller keeps
    *p's arrays alive until me_ba_wait, which blocks on this solve only (not on

@@ -254,6 +254,11 @@ int plan_build(me_ctx* c, const me_ba_problem* p, const me_ba_options* opt, Plan
   o.max_diag = opt->max_lm_diagonal;
   o.min_rel_decrease = opt->min_relative_decrease;
   o.max_invalid = opt->max_num_consecutive_invalid_steps;
+  // The closing linearisation (the enqueue after max_num_iterations steps) leaves two things: x_cost, which the
+  // last accepted step's decision already set to its candidate cost, and the gradient-tolerance test.  With the
+  // tolerance off that test fires only on a gradient of exact zeros, so the pass is not queued and the last step's
+  // decision ends the solve (close_t).  Without iterations it is the only linearisation (the initial cost): kept.
+  o.close_in_decide = opt->gradient_tolerance > 0.0 || opt->max_num_iterations == 0 ? 0 : 1;
   const bool dev = p->mem == ME_DEVICE;
   // one arena; the five inputs first and contiguous (one H2D for host input)
   const long nb = g.pstride;
@@ -525,6 +530,7 @@ int enqueue_assemble(Plan& P, bool img = false) {
 // ends the solve (iterations == max_num_iterations), so the camera solve and
 // the point step that would follow are never run: they are not queued (two
 // no-op launches fewer per solve; every rank of a sharded solve skips alike).
+// A plan with Opts::close_in_decide queues no such pass at all (lin_passes).
 int enqueue_iteration(Plan& P, bool last = false) {
   me_ctx* c = P.c;
   const Geo& g = P.g;
@@ -588,6 +594,14 @@ int enqueue_iteration(Plan& P, bool last = false) {
     hipLaunchKernelGGL(decide_kernel, dim3(1), dim3(64), 0, s, g, P.b, P.o);
   }
   return me_check_launch(c, "BA iteration");
+}
+
+// The enqueue_iteration calls of a whole solve: max_num_iterations iterations
+// and, unless the last step's decision ends the solve (Opts::close_in_decide),
+// the closing pass (`last`).  It follows from the options alone, so every rank
+// of a sharded solve queues the same collectives.
+inline int lin_passes(const Plan& P) {
+  return P.o.max_num_iterations + (P.o.close_in_decide ? 0 : 1);
 }
 
 // Final state (and host parameters) -> pinned staging; enqueued behind the
@@ -663,9 +677,10 @@ int solve_impl(me_ctx* c, me_ba_problem* p, const me_ba_options* opt, me_comm* c
   // the host polls; after convergence at most one chunk of no-op launches
   // (every kernel tests State::done first) is left in the queue.
   const int chunk = 4;
+  const int passes = lin_passes(P);
   int it = 0;
   auto enqueue_chunk = [&](int slot) -> int {
-    for (int k = 0; k < chunk && it <= opt->max_num_iterations; ++k, ++it)
+    for (int k = 0; k < chunk && it < passes; ++k, ++it)
       ME_TRY(enqueue_iteration(P, it == opt->max_num_iterations));
     ME_HIP(c, hipMemcpyAsync(P.hstate[slot], P.b.st, sizeof(State), hipMemcpyDeviceToHost, c->stream));
     ME_HIP(c, hipEventRecord(c->poll_ev[slot], c->stream));
@@ -674,15 +689,15 @@ int solve_impl(me_ctx* c, me_ba_problem* p, const me_ba_options* opt, me_comm* c
   // once the last possible chunk is queued, the output follows it at once
   bool out_q = false;
   ME_TRY(enqueue_chunk(0));
-  if (it > opt->max_num_iterations) {
+  if (it >= passes) {
     ME_TRY(enqueue_output(P, p));
     out_q = true;
   }
   for (int cur = 0;; cur ^= 1) {
-    const bool more = it <= opt->max_num_iterations;
+    const bool more = it < passes;
     if (more) {
       ME_TRY(enqueue_chunk(cur ^ 1));
-      if (it > opt->max_num_iterations) {
+      if (it >= passes) {
         ME_TRY(enqueue_output(P, p));
         out_q = true;
       }
@@ -792,7 +807,7 @@ static int solve_async_impl(me_ctx* c, me_ba_problem* p, const me_ba_options* op
   int rc = plan_build(c, p, opt, A->P, A->set, A->set);
   A->P.copy_out = copy_out && A->P.dev;
   if (rc == ME_OK) {
-    for (int it = 0; it <= opt->max_num_iterations && rc == ME_OK; ++it)
+    for (int it = 0; it < lin_passes(A->P) && rc == ME_OK; ++it)
       rc = enqueue_iteration(A->P, it == opt->max_num_iterations);
   }
   if (rc == ME_OK) rc = enqueue_output(A->P, &A->prob);

@@ -88,16 +88,34 @@ __device__ __forceinline__ void decide_t(S& st, const double* scal, const Opts& 
   }
 }
 
-__device__ void decide(Bufs& b, const Opts& o) { decide_t(*b.st, b.scal, o); }
+// The end of a solve whose closing linearisation is not queued
+// (Opts::close_in_decide), behind decide_t on every one of its returns: the
+// iteration-limit test the closing lin_finalize would have run at the head of
+// iteration max_num_iterations + 1 (ahead of the minimum-radius test, as
+// there).  A solve decide_t itself ended keeps its termination.
+template <class S>
+__device__ __forceinline__ void close_t(S& st, const Opts& o) {
+  if (o.close_in_decide && !st.done && st.iterations >= o.max_num_iterations) {
+    st.done = 1;
+    st.termination = 1;
+  }
+}
+
+__device__ void decide(Bufs& b, const Opts& o) {
+  decide_t(*b.st, b.scal, o);
+  close_t(*b.st, o);
+}
 
 // The fields decide_t reads or writes, loaded by the finalizing thread in one
 // round before the partial reduce (round 6: the decision's dependent State
 // loads were half of the step's finalize tail, ME_STEP_TS)
 struct DecideState {
   int cur, need_lin, done, termination, successful, invalid_count, fail, accepted, spin_err;
+  int iterations;  // (read only: close_t)
   double radius, decrease, x_cost, cand_cost, model_change, cam_step2, cam_xn2, cam_model, last_q;
   __device__ __forceinline__ void load(const State* st) {
     cur = st->cur; need_lin = st->need_lin; done = st->done; termination = st->termination;
+    iterations = st->iterations;
     successful = st->successful; invalid_count = st->invalid_count; fail = st->fail; accepted = st->accepted;
     spin_err = st->spin_err; radius = st->radius; decrease = st->decrease; x_cost = st->x_cost;
     cand_cost = st->cand_cost; model_change = st->model_change; last_q = st->last_q;
@@ -200,6 +218,7 @@ __device__ void step_finalize_body(const Geo& g, Bufs b, const Opts& o, int do_d
     for (int k = R_MODEL; k <= R_COUNT; ++k) b.scal[k] = scal[k];
     if (do_decide) {
       decide_t(ds, scal, o);
+      close_t(ds, o);
       ds.store(st);
     }
 #ifdef ME_STEP_TS
@@ -305,7 +324,8 @@ __device__ void rot_step_body(const Geo& g, const Bufs& b, int cur) {
 }
 
 // Grid: g.nblk_step point workgroups + the camera workgroup (cam_step_body,
-// then rot_step_body behind its arrival).
+// then rot_step_body behind its arrival; not in the last iteration of a solve
+// that queues no closing linearisation, Opts::close_in_decide).
 template <int OD>
 __global__ __launch_bounds__(kStepBlock) void pt_step_kernel(Geo g, Bufs b, Opts o, int do_decide) {
   __shared__ double lds[16];
@@ -322,6 +342,8 @@ __global__ __launch_bounds__(kStepBlock) void pt_step_kernel(Geo g, Bufs b, Opts
   // flips cur and clears fail)
   const bool cam_wg = (int)blockIdx.x == g.nblk_step && !st->fail;
   const int cam_cur = st->cur;
+  // (the last iteration of a solve without a closing linearisation: nothing reads the candidates' table)
+  const bool rot_wg = cam_wg && !(o.close_in_decide && st->iterations >= o.max_num_iterations);
   if ((int)blockIdx.x == g.nblk_step) {
     // (thread 0's scalar stores drain before its arrival, last_arrival_wt)
     if (cam_wg) cam_step_body(g, b, cam_cur, lds);
@@ -507,7 +529,7 @@ __global__ __launch_bounds__(kStepBlock) void pt_step_kernel(Geo g, Bufs b, Opts
   // the last workgroup to finish (of either kind) reduces the partials
   // (step_finalize) and, single-GPU, runs the Ceres step handling
   if (!last_arrival_wt(b.cnt + g.m, gridDim.x)) {
-    if (cam_wg) rot_step_body(g, b, cam_cur);
+    if (rot_wg) rot_step_body(g, b, cam_cur);
     return;
   }
 #ifdef ME_STEP_TS
@@ -518,7 +540,7 @@ __global__ __launch_bounds__(kStepBlock) void pt_step_kernel(Geo g, Bufs b, Opts
 #ifdef ME_STEP_TS
   if (threadIdx.x == 0) atomicAdd(&g_step_ts[7], 1ull);
 #endif
-  if (cam_wg) rot_step_body(g, b, cam_cur);  // (the camera workgroup arrived last: the table behind the step's decision)
+  if (rot_wg) rot_step_body(g, b, cam_cur);  // (the camera workgroup arrived last: the table behind the step's decision)
 }
 
 __global__ void decide_kernel(Geo g, Bufs b, Opts o) {

@@ -47,6 +47,10 @@ struct Opts {
   double function_tolerance, gradient_tolerance, parameter_tolerance;
   double initial_radius, max_radius, min_radius, min_diag, max_diag, min_rel_decrease;
   int max_invalid;
+  // No closing linearisation is queued (plan_build: gradient_tolerance <= 0 and max_num_iterations > 0): the step
+  // decision of iteration max_num_iterations ends the solve itself (close_t, ba_step.hpp), and that iteration's
+  // camera workgroup builds no rotation table.  One word for the host's queueing and the device's decision.
+  int close_in_decide;
 };
 
 struct State {
