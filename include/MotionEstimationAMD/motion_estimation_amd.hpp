@@ -257,14 +257,18 @@ class BundleAdjuster {
       return status_ = Status::FAILED;
     }
     if (calib_.compute_cov) {
-      std::vector<double> cov(36 * cams_.size());
+      // one pass for the pose blocks and the landmark blocks the reference declares and leaves empty
+      // (m_point_covs, BundleAdjuster.h:277,498-523): both fill, or neither
+      std::vector<double> cov(36 * cams_.size()), pc(9 * pts_.size());
       int ok = 0;
-      rc = me_ba_covariance(ctx_->get(), &p, cov.data(), &ok);
+      rc = me_ba_covariance_full(ctx_->get(), &p, cov.data(), pc.data(), &ok);
       if (rc != ME_OK || !ok) {
         std::cerr << "[Bundle Adjuster] error computing the covariance matrix" << std::endl;
       } else {
         covs_.assign(cams_.size(), {});
         for (size_t i = 0; i < cams_.size(); ++i) std::copy(&cov[36 * i], &cov[36 * i] + 36, covs_[i].begin());
+        pt_covs_.assign(pts_.size(), {});
+        for (size_t j = 0; j < pts_.size(); ++j) std::copy(&pc[9 * j], &pc[9 * j] + 9, pt_covs_[j].begin());
       }
     }
     return status_ = (summary_.status == 2 ? Status::SUCCESSFUL : Status::FAILED);
@@ -274,6 +278,8 @@ class BundleAdjuster {
   const std::vector<std::array<double, 6>>& getCameraParams() const { return cams_; }
   // 6x6 row-major per camera (empty unless compute_cov and the covariance succeeded)
   const std::vector<std::array<double, 36>>& getPosesCovariance() const { return covs_; }
+  // 3x3 row-major per landmark, filled with the pose covariances (BundleAdjuster.h:239 getPointsCovariance)
+  const std::vector<std::array<double, 9>>& getPointsCovariance() const { return pt_covs_; }
   int getNbPoints() const { return (int)pts_.size(); }
   int getNbCameras() const { return (int)cams_.size(); }
   int getNbObservations() const { return (int)obs_.size(); }
@@ -291,6 +297,7 @@ class BundleAdjuster {
   std::vector<std::array<double, 3>> pts_;
   std::vector<Observation<M>> obs_;
   std::vector<std::array<double, 36>> covs_;
+  std::vector<std::array<double, 9>> pt_covs_;
   amd::Context* ctx_;
   Status status_ = Status::UNINITIALISED;
   me_ba_options opts_ = defaults();
@@ -1189,6 +1196,43 @@ class WindowedStereoVO {
     X.resize((size_t)n);
     check(me_vo_loop_tracks(v_.get(), ids.data(), n ? X[0].data() : nullptr, nullptr, nullptr, nullptr, n, &n),
           "tracks");
+  }
+  // The window covariance (me_vo_loop_set_covariance): every window's
+  // covariance queued behind its solve and read back with it; landmarks also
+  // computes the landmark blocks.  Off by default; before the first frame, a
+  // later call throws.  Read only: events, poses and results do not change.
+  void setCovariance(bool on, bool landmarks = true) {
+    const me_vo_cov_params p{landmarks ? 1 : 0};
+    check(me_vo_loop_set_covariance(v_.get(), on ? &p : nullptr), "WindowedStereoVO::setCovariance");
+  }
+  // 6x6 row-major covariance of keyframe t's pose {t, angle-axis}: the last
+  // camera's block of t's own window, in the BA's gauge (the window's first
+  // fixed_frames cameras constant).  false: no such window yet, the switch is
+  // off, or its solve / covariance failed (cov is then zeros).
+  bool pose_cov(int t, std::array<double, 36>& cov) const {
+    int n = 0;
+    check(me_vo_loop_pose_covs(v_.get(), nullptr, nullptr, nullptr, 0, &n), "pose_cov");
+    std::vector<int32_t> ts((size_t)n);
+    std::vector<double> c(36 * (size_t)n);
+    std::vector<uint8_t> ok((size_t)n);
+    check(me_vo_loop_pose_covs(v_.get(), ts.data(), c.data(), ok.data(), n, &n), "pose_cov");
+    cov.fill(0.0);
+    for (int i = 0; i < n; ++i)
+      if (ts[i] == t) {
+        std::copy(&c[36 * (size_t)i], &c[36 * (size_t)i] + 36, cov.begin());
+        return ok[i] != 0;
+      }
+    return false;
+  }
+  // per live track (the order of tracks()): its landmark's 3x3 row-major
+  // covariance from the latest window that held it, and whether it is known
+  void track_cov(std::vector<int64_t>& ids, std::vector<std::array<double, 9>>& cov, std::vector<uint8_t>& ok) const {
+    int n = 0;
+    check(me_vo_loop_track_covs(v_.get(), nullptr, nullptr, nullptr, 0, &n), "track_cov");
+    ids.resize((size_t)n);
+    cov.resize((size_t)n);
+    ok.resize((size_t)n);
+    check(me_vo_loop_track_covs(v_.get(), ids.data(), n ? cov[0].data() : nullptr, ok.data(), n, &n), "track_cov");
   }
 
  private:

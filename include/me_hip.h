@@ -377,8 +377,18 @@ int me_ba_wait(me_ctx* ctx, me_ba_summary* s);
    NULL): read back behind the solve, so the wait does not block on work
    queued after it. */
 int me_ba_wait_out(me_ctx* ctx, me_ba_summary* s, double* cams, double* pts);
-/* Sizes the ctx's BA scratch and page-locked staging (synchronous and both
-   asynchronous sets) for windows up to these sizes, so a growing window does
+/* me_ba_wait_out, and the window covariance that me_vo_window_submit queued
+   behind the solve (me_vo_window.cov), from the same staging: cam_cov
+   (n_cams*36) and pt_cov (n_pts*9, written only when cov was 2) as
+   me_ba_covariance_full gives them at the cams / pts the solve left.
+   *cov_ok = the queued mode (1 or 2) when the covariance succeeded, else 0
+   with both arrays untouched (none queued, ok = 0, or the wait failed).  Any
+   of the three may be NULL. */
+int me_ba_wait_out_cov(me_ctx* ctx, me_ba_summary* s, double* cams, double* pts, double* cam_cov, double* pt_cov,
+                       int* cov_ok);
+/* Sizes the ctx's BA scratch and page-locked staging (synchronous, both
+   asynchronous sets and the window covariance's set, me_ba_covariance_full)
+   for windows up to these sizes, so a growing window does
    not reallocate (a reallocation waits for the ctx stream).  No solve may be
    queued. */
 int me_ba_reserve(me_ctx* ctx, int n_cams, int n_pts, int n_obs, int obs_dim, int fixed_frames);
@@ -428,6 +438,9 @@ typedef struct me_vo_window {
   const int32_t* frame;
   const int32_t* ids;
   int first_frame;
+  int cov; /* 0: none.  1 / 2: the window covariance (camera blocks / also landmark blocks, me_ba_covariance_full)
+              queued directly behind the solve on the ctx stream, in scratch of its own, read back into the solve's
+              staging ahead of its event: me_ba_wait_out_cov returns it with the solve's result, no further wait */
 } me_vo_window;
 int me_vo_window_submit(me_ctx* ctx, const me_vo_window* w, me_ba_problem* p, const me_ba_options* o);
 /* ---- the windowed stereo VO loop, native (round 5) ----------------------
@@ -498,6 +511,28 @@ int me_vo_loop_set_match_lr(me_vo_loop* v, double lr_max);
    without this setter.  Other values: ME_ERR_INVALID; after the first
    me_vo_loop_process: ME_ERR_STATE. */
 int me_vo_loop_set_klt_predict(me_vo_loop* v, int on);
+/* Window covariance (NULL: off, the default; set before the first frame).
+   Every window's covariance is queued on the BA context's stream directly
+   behind that window's solve and ahead of the next window's submission,
+   evaluated at the cams and pts the solve leaves, and read back with the
+   solve's own result: no extra host wait per keyframe, and read only (events,
+   poses and results are those of the loop without it).  The gauge is the
+   BA's own: the window's first fixed_frames cameras are constant, so their
+   blocks are zero and every block is relative to them.  landmarks != 0 also
+   computes the landmark blocks.
+   me_vo_loop_pose_covs: per keyframe t that had a window of its own, the
+   6x6 block of that window's last camera (cov36, row-major) and ok.
+   me_vo_loop_track_covs: per live track (the order of me_vo_loop_tracks), the
+   3x3 block from the latest window that held it (cov9) and ok.  A failed
+   solve (termination 2) or a covariance with ok = 0 leaves zeros with ok = 0
+   and does not stop the loop.  Both readers: *n = entries, at most cap
+   written; outputs may be NULL. */
+typedef struct me_vo_cov_params {
+  int landmarks;
+} me_vo_cov_params;
+int me_vo_loop_set_covariance(me_vo_loop* v, const me_vo_cov_params* p);
+int me_vo_loop_pose_covs(me_vo_loop* v, int32_t* ts, double* cov36, uint8_t* ok, int cap, int* n);
+int me_vo_loop_track_covs(me_vo_loop* v, int64_t* ids, double* cov9, uint8_t* ok, int cap, int* n);
 /* Rectification inside the loop (A12d): with two camera models the loop builds
    their maps once on the front context -- the rectified model is the loop's
    own width, height and K (fx = K[0], fy = K[4], cx = K[2], cy = K[5]) -- and
@@ -668,6 +703,24 @@ int me_ba_reduced_system(me_ctx* ctx, const me_ba_problem* p, double radius, dou
    get zero blocks as in Ceres.  *ok = 0 (and cov untouched) when J^T J is not
    positive definite (Ceres reports a rank-deficient Jacobian). */
 int me_ba_covariance(me_ctx* ctx, const me_ba_problem* p, double* cov /* n_cams*36 */, int* ok);
+/* Window covariance: the camera blocks of me_ba_covariance and the landmark
+   blocks the reference declares and never fills (getPointsCovariance /
+   m_point_covs, BundleAdjuster.h:239,277; their computation is commented out
+   at :498-523).  pt_cov[9 j .. 9 j + 8] = 3x3 row-major block j of (J^T J)^-1,
+   by the Schur form: V_j^-1 + sum_a sum_b T_a^T Sigma_cc[a, b] T_b with
+   T_a = (Jc^T Jp) V_j^-1 over landmark j's observations in variable cameras
+   (loss-corrected rows); a landmark seen only by constant cameras gets V_j^-1.
+   The gauge is the BA's own: the first fixed_frames cameras are constant and
+   their blocks zero.  Either output may be NULL, not both.  *ok = 0 (outputs
+   untouched) exactly where me_ba_covariance reports 0, and when a V_j is not
+   positive definite.
+   ME_HOST problems: host outputs, the call returns with them.  ME_DEVICE
+   problems: cam_cov, pt_cov and ok are device pointers and the call is
+   asynchronous on the ctx stream; it does not wait for solves queued on the
+   ctx (me_ba_solve_async) and works in a scratch set of its own, which
+   me_ba_reserve also sizes. */
+int me_ba_covariance_full(me_ctx* ctx, const me_ba_problem* p, double* cam_cov /* n_cams*36 or NULL */,
+                          double* pt_cov /* n_pts*9 or NULL */, int* ok);
 
 /* ---- §8e: landmark-sharded BA over several GPUs ----------------------
  * No reference counterpart (the reference solves on one CPU thread); the

@@ -50,6 +50,12 @@ loads another build of libme_hip.so (tools/build_variant.sh).
                          call, me_kf_update and me_motion_gate on the same features beside it, and a config-3 push loop over N camera frames (three per keyframe
                          step of the arc) with the frame pose off / on, alternating.  --trace 1: the calls alone,
                          no event timing (the run rocprofv3 --kernel-trace --stats wraps)
+  window_cov [CONFIGS --reps --repeats --trace --loop N]
+                         me_ba_covariance beside me_ba_covariance_full (cameras only / with landmarks, host and
+                         device-resident form) on the configs' windows (3,5) after a 10-iteration solve: wall time
+                         per call, and the config-3 native loop with the covariance switch off / cameras /
+                         cameras and landmarks, alternating.  --trace 1: the calls alone (under rocprofv3
+                         --kernel-trace --stats)
 """
 import argparse
 import ctypes
@@ -1562,6 +1568,78 @@ def cmd_frame_pose(a):
     print(json.dumps(out))
 
 
+def cmd_window_cov(a):
+    """me_ba_covariance (cameras, the one-workgroup global-memory factor) beside me_ba_covariance_full (cameras only /
+    with landmarks; host form and the queued device-resident form) on a config's window after 10 LM iterations: wall
+    time per call, the plan and linearisation included (the same for every entry).  The kernels' own times come from
+    a rocprofv3 --kernel-trace --stats run of --trace 1 (few calls, nothing timed)."""
+    from uasl_motion_estimation_amd.optimisation import (DeviceBAProblem, SolverOptions, ba_covariance,
+                                                         ba_covariance_full, ba_solve)
+    ctx = _setup(a.lib)
+    for c in a.configs.split(","):
+        bp = _ba_problem(c)
+        bp.cams, bp.pts, _ = ba_solve(bp, SolverOptions.fixed_iterations(10), ctx=ctx)
+        dev = DeviceBAProblem(bp, ctx)
+        calls = {
+            "me_ba_covariance": lambda: ba_covariance(bp, ctx=ctx),
+            "me_ba_covariance_full[cameras]": lambda: ba_covariance_full(bp, ctx=ctx, landmarks=False),
+            "me_ba_covariance_full[cameras+landmarks]": lambda: ba_covariance_full(bp, ctx=ctx),
+            "me_ba_covariance_full[device, cameras]": lambda: dev.covariance_full_async(landmarks=False),
+            "me_ba_covariance_full[device, cameras+landmarks]": lambda: dev.covariance_full_async(),
+        }
+        nf = min(max(bp.fixed_frames, 0), len(bp.cams))
+        shape = {"config": c, "cams": len(bp.cams), "pts": len(bp.pts), "obs": len(bp.obs), "n6": 6 * (len(bp.cams) - nf)}
+        for name, f in calls.items():
+            r = f()
+            ctx.synchronize()
+            ok = dev.covariance_read()[0] if "device" in name else int(r is not None)
+            if a.trace:
+                for _ in range(a.reps):
+                    f()
+                ctx.synchronize()
+                continue
+            for rep in range(a.repeats):
+                ctx.synchronize()
+                w0 = time.perf_counter()
+                for _ in range(a.reps):
+                    f()
+                ctx.synchronize()
+                print(json.dumps(dict(shape, call=name, repeat=rep, ok=ok,
+                                      wall_us_per_call=round((time.perf_counter() - w0) / a.reps * 1e6, 2))), flush=True)
+        dev.close()
+    if a.loop > 0 and not a.trace:  # the config-3 native loop with the switch off / cameras / cameras and landmarks
+        import torch
+
+        from uasl_motion_estimation_amd import pipeline as PL
+        from uasl_motion_estimation_amd import synthetic as S
+        from uasl_motion_estimation_amd.ba_cov import WindowCovariance
+        NK = a.loop
+        arc = S.trajectory_arc(max(NK, 2))
+        truth = [np.concatenate([t, S.R_to_aa_robust(R)]) for (R, t) in arc]
+        K = S.intrinsics(1280, 720)
+        frames = []
+        for c0 in range(0, NK, 50):
+            _, fr = S.corridor_frames_torch(S.SEED0 + 3, 1280, 720, c0, min(50, NK - c0))
+            frames += [(Lk.contiguous(), Rk.contiguous()) for (Lk, Rk, _, _) in fr]
+            torch.cuda.synchronize()
+        for rep_ in range(-1, a.repeats):  # (-1: a short untimed run, the first loop of a process pays the allocations)
+            for name, cov in (("off", None), ("cameras", WindowCovariance(landmarks=False)),
+                              ("cameras+landmarks", WindowCovariance())):
+                cfg = PL.PipelineConfig.from_config(3, covariance=cov)
+                vo = PL.NativeStereoVO(cfg, ctx, K, truth[0], truth[1] - truth[0], log_events=False, overlap=True)
+                t0 = time.perf_counter()
+                for t in range(NK if rep_ >= 0 else min(NK, 30)):
+                    vo.process(t, *frames[t])
+                vo.finish()
+                dt = time.perf_counter() - t0
+                okc = vo.pose_cov_ok()
+                vo.close()
+                if rep_ >= 0:
+                    print(json.dumps({"covariance": name, "repeat": rep_, "keyframes": NK,
+                                      "keyframes_per_s": round(NK / dt, 2), "us_per_keyframe": round(1e6 * dt / NK, 1),
+                                      "windows_ok": int(sum(okc.values())), "windows": len(okc)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--lib", default=os.environ.get("ME_LIB"))
@@ -1636,6 +1714,12 @@ def main():
     p.add_argument("--check", type=int, default=1)
     p.add_argument("--trace", type=int, default=0, help="1: the calls alone, no event timing (under rocprofv3)")
     p.add_argument("--loop", type=int, default=200, help="camera frames of the config-3 native push loop per run (0: skip)")
+    p = sub.add_parser("window_cov")
+    p.add_argument("configs", nargs="?", default="3,5")
+    p.add_argument("--reps", type=int, default=50)
+    p.add_argument("--repeats", type=int, default=3)
+    p.add_argument("--trace", type=int, default=0, help="1: the calls alone, nothing timed (under rocprofv3)")
+    p.add_argument("--loop", type=int, default=200, help="keyframes of the config-3 native loop per run (0: skip)")
     a = ap.parse_args()
     globals()["cmd_" + a.cmd](a)
 

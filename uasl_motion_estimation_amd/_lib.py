@@ -119,7 +119,12 @@ class VOWindowC(ctypes.Structure):
     _fields_ = [("stage", c_void_p), ("dev", c_void_p), ("stage_bytes", c_size_t), ("chain", c_int),
                 ("cam_src", c_void_p), ("win_ids", c_void_p), ("prev_ids", c_void_p), ("n_prev", c_int),
                 ("new_from", ctypes.c_int32), ("args", VOChainArgsC), ("frame", c_void_p), ("ids", c_void_p),
-                ("first_frame", c_int)]
+                ("first_frame", c_int), ("cov", c_int)]
+
+
+class VOCovParamsC(ctypes.Structure):
+    """me_vo_cov_params (include/me_hip.h)."""
+    _fields_ = [("landmarks", c_int)]
 
 
 class VOLoopConfigC(ctypes.Structure):
@@ -211,7 +216,7 @@ EXPORTS = [
     "me_optim_default_params", "me_scale_residuals", "me_scale_normal_equations", "me_scale_jacobian",
     "me_scale_optimise", "me_scale_last_counters", "me_scale_persistent", "me_scale_state_mi", "me_scale_inliers",
     "me_ba_default_options", "me_ba_solve", "me_ba_cost", "me_ba_evaluate", "me_ba_reduced_system",
-    "me_ba_solve_sharded", "me_ba_covariance", "me_ba_solve_async", "me_ba_wait", "me_ba_wait_out", "me_ba_reserve", "me_ba_window_indices",
+    "me_ba_solve_sharded", "me_ba_covariance", "me_ba_covariance_full", "me_ba_solve_async", "me_ba_wait", "me_ba_wait_out", "me_ba_reserve", "me_ba_window_indices",
     "me_vo_ba_chain", "me_vo_window_submit",
     "me_comm_unique_id", "me_comm_create_rccl", "me_comm_create_callback", "me_comm_destroy", "me_comm_info",
     "me_comm_allreduce", "me_comm_calibrate", "me_comm_exchange_us", "me_ba_shard_worthwhile_comm", "me_ba_solve_comm", "me_ba_shard_worthwhile", "me_ba_shard_exchange_us",
@@ -228,7 +233,8 @@ EXPORTS = [
     "me_vo_loop_process", "me_vo_loop_finish", "me_vo_loop_results", "me_vo_loop_events", "me_vo_loop_tracks",
     "me_vo_loop_poses", "me_vo_loop_frame_obs", "me_vo_loop_frames", "me_vo_loop_stats", "me_vo_loop_set_match_lr",
     "me_motion_gate_default_params", "me_motion_gate", "me_vo_loop_set_motion_gate",
-    "me_vo_loop_set_klt_predict",
+    "me_vo_loop_set_klt_predict", "me_vo_loop_set_covariance", "me_vo_loop_pose_covs", "me_vo_loop_track_covs",
+    "me_ba_wait_out_cov",
     "me_kf_default_params", "me_kf_update", "me_vo_loop_set_keyframe_select", "me_vo_loop_push",
     "me_frame_pose_default_params", "me_frame_pose", "me_vo_loop_set_frame_pose", "me_vo_loop_frame_poses",
 ]
@@ -340,6 +346,7 @@ def load_library(path: str | None = None):
         "me_ba_evaluate": (c_int, [c_void_p, P(BAProblemC), P(c_double), P(c_double), P(c_double)]),
         "me_ba_reduced_system": (c_int, [c_void_p, P(BAProblemC), c_double, P(c_double), P(c_double)]),
         "me_ba_covariance": (c_int, [c_void_p, P(BAProblemC), P(c_double), P(c_int)]),
+        "me_ba_covariance_full": (c_int, [c_void_p, P(BAProblemC), c_void_p, c_void_p, c_void_p]),
         "me_ba_solve_sharded": (c_int, [c_void_p, P(BAProblemC), P(BAOptionsC), ALLREDUCE_FN, c_void_p,
                                         P(BASummaryC)]),
         "me_comm_unique_id": (c_int, [c_void_p, c_int]),
@@ -360,6 +367,10 @@ def load_library(path: str | None = None):
         "me_vo_loop_destroy": (None, [c_void_p]),
         "me_vo_loop_set_match_lr": (c_int, [c_void_p, c_double]),
         "me_vo_loop_set_klt_predict": (c_int, [c_void_p, c_int]),
+        "me_vo_loop_set_covariance": (c_int, [c_void_p, c_void_p]),
+        "me_vo_loop_pose_covs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, P(c_int)]),
+        "me_vo_loop_track_covs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, P(c_int)]),
+        "me_ba_wait_out_cov": (c_int, [c_void_p, P(BASummaryC), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
         "me_vo_loop_last_error": (ctypes.c_char_p, [c_void_p]),
         "me_vo_loop_process": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int]),
         "me_vo_loop_finish": (c_int, [c_void_p]),

@@ -23,6 +23,7 @@
 #include "ba_cam_solve.hpp"
 #include "ba_step.hpp"
 #include "ba_eval.hpp"
+#include "ba_cov.hpp"
 #include "ba_plan.hpp"
 #include "ba_vo_chain.hpp"
 
@@ -87,6 +88,9 @@ struct Plan {
   SchurKernel schur = nullptr;  // the pt_schur_kernel instance of this geometry (schur_instance)
   bool fused_lin = false;   // the plan's Schur instance linearises in its phase A: no linearize_kernel launch, no obsx
   bool full_S = false;      // assemble both block triangles of S (reduced-system / covariance read-back)
+  size_t cov_off = 0;       // asynchronous plans: where the staging holds a covariance queued behind the solve (doubles)
+  bool cov = false;         // me_ba_covariance_full: a device-resident problem's plan queues behind the asynchronous
+                            // solves (no drain) and takes no host staging
   int solve_cap = 0;        // co-resident cam_solve_kernel<2> workgroups on the ctx's CUs (0: not queried)
   me_comm* comm = nullptr;  // sharded solve: the exchange (null: one GPU)
   bool xmax_separate = false;  // ABI-v2 callback (no rank): the gradient max-norm travels in its own max all-reduce
@@ -176,7 +180,8 @@ int ba_drain(me_ctx* c);
 // every other plan first completes the queued solves (they own the scratch)
 int plan_build(me_ctx* c, const me_ba_problem* p, const me_ba_options* opt, Plan& P, int slot_base,
                int async = -1, me_comm* comm = nullptr) {
-  if (async < 0) ME_TRY(ba_drain(c));
+  const bool cov_dev = P.cov && p->mem == ME_DEVICE;
+  if (async < 0 && !cov_dev) ME_TRY(ba_drain(c));
   ME_CHECK(c, p->n_cams > 0 && p->n_pts >= 0 && p->n_obs >= 0, "BA: bad sizes");
   ME_CHECK(c, p->n_cams <= kMaxScanCams, "BA: at most %d cameras per window", kMaxScanCams);
   ME_CHECK(c, p->obs_dim == 0 || p->obs_dim == 2 || p->obs_dim == 4, "BA: obs_dim must be 2 or 4 (Observation<M>)");
@@ -195,7 +200,7 @@ int plan_build(me_ctx* c, const me_ba_problem* p, const me_ba_options* opt, Plan
   P.c = c;
   // the ctx's test-hook word (me_debug_solve_flags): the host-only bits are translated here
   int hook = c->dbg_solve_flags;
-  if ((hook & kFlagFailEveryOther) && (c->dbg_solve_count++ & 1)) hook |= kFlagSolveFail;
+  if ((hook & kFlagFailEveryOther) && !P.cov && (c->dbg_solve_count++ & 1)) hook |= kFlagSolveFail;  // (solves only)
   P.no_fused_asm = (hook & kFlagSeparateAsm) != 0;
   P.solve_flags = hook & (kFlagAsmTimeout | kFlagSolveFail | kFlagRosterNow);
   Geo& g = P.g;
@@ -341,8 +346,11 @@ int plan_build(me_ctx* c, const me_ba_problem* p, const me_ba_options* opt, Plan
   b.roster = b.cnt + g.m + 4;
   b.bvec = b.S + (size_t)g.n6 * g.n6;
   b.diagU = b.bvec + g.n6;
-  void* hp;
-  const size_t stage = rup((long)std::max(8 * out_doubles, dev ? (size_t)0 : input_span), 64);
+  void* hp = nullptr;
+  // (an asynchronous solve's staging also takes the window covariance queued behind it: cam | fail | pt blocks)
+  const size_t cov_doubles = async >= 0 ? 36 * (size_t)g.nc + 1 + 9 * (size_t)g.np : 0;
+  P.cov_off = out_doubles;
+  const size_t stage = rup((long)std::max(8 * (out_doubles + cov_doubles), dev ? (size_t)0 : input_span), 64);
   const size_t hbytes = stage + 2 * rup(sizeof(State), 64);
   if (async >= 0) {  // staging owned by the asynchronous solve (set `async` is free: its last solve was waited)
     if (c->ba_pinned_size[async] < hbytes) {
@@ -353,7 +361,7 @@ int plan_build(me_ctx* c, const me_ba_problem* p, const me_ba_options* opt, Plan
       c->ba_pinned_size[async] = std::max(hbytes, (size_t)4096);
     }
     hp = c->ba_pinned[async];
-  } else {
+  } else if (!cov_dev) {
     ME_TRY(me_pinned(c, hbytes, &hp));
   }
   P.host = (double*)hp;
@@ -721,6 +729,7 @@ struct AsyncSolve {
   int set = 0;  // scratch / staging set
   bool completed = false;
   int rc = ME_OK;
+  int cov = 0;  // window covariance queued behind the solve (solve_async_impl): staged at P.host + P.cov_off
   me_ba_summary sum{};
 };
 constexpr int kBaQueue = 2;
@@ -783,12 +792,37 @@ AsyncSolve* ba_chain_source(AsyncQueue* Q) {
   return Q->n ? Q->q[Q->n - 1] : Q->last;
 }
 
+// The window covariance's own scratch (beside the solves' sets 0 and 1, so a
+// solve queued on the ctx may run behind it): the plan's arena in set 2, and
+// Sigma_cc | camera blocks | the two failure words (one double) | landmark
+// blocks: a host problem reads back from the camera blocks on, up to the
+// failure words when no landmark block was asked for.
+constexpr int kCovSet = 2, kCovOutSlot = SLOT_COUNT + 3;
+struct CovOut {
+  double *Sig, *cam, *pt;
+  int* fail;
+};
+int cov_out(me_ctx* c, const Geo& g, CovOut& o) {
+  const size_t nsig = (size_t)g.n6 * g.n6, ncam = 36 * (size_t)g.nc, npt = 9 * (size_t)g.np;
+  void* d;
+  ME_TRY(me_scratch(c, kCovOutSlot, 8 * (nsig + ncam + 1 + npt) + 64, &d));
+  o.Sig = (double*)d;
+  o.cam = o.Sig + nsig;
+  o.fail = (int*)(o.cam + ncam);
+  o.pt = o.cam + ncam + 1;
+  return ME_OK;
+}
+
 }  // namespace
 
 // copy_out: a device-resident problem's solved cams / pts also read back
 // into the staging behind the solve (me_vo_window_submit; me_ba_wait_out
 // then returns them without touching the stream)
-static int solve_async_impl(me_ctx* c, me_ba_problem* p, const me_ba_options* opt, bool copy_out) {
+static int cov_enqueue(me_ctx* c, const me_ba_problem* p, bool want_pts, CovOut& out, Geo& gout);
+
+// cov: 0 none, 1 the window covariance's camera blocks, 2 also its landmark blocks, queued behind the solve's
+// output at the cams / pts it leaves and read back into the solve's staging (me_ba_wait_out_cov) ahead of its event
+static int solve_async_impl(me_ctx* c, me_ba_problem* p, const me_ba_options* opt, bool copy_out, int cov = 0) {
   if (!c || !p || !opt) return ME_ERR_INVALID;
   ME_HIP(c, hipSetDevice(c->device));
   AsyncQueue* Q = ba_queue(c);
@@ -811,6 +845,15 @@ static int solve_async_impl(me_ctx* c, me_ba_problem* p, const me_ba_options* op
       rc = enqueue_iteration(A->P, it == opt->max_num_iterations);
   }
   if (rc == ME_OK) rc = enqueue_output(A->P, &A->prob);
+  if (rc == ME_OK && cov && A->P.dev) {
+    CovOut out;
+    Geo g;
+    rc = cov_enqueue(c, &A->prob, cov == 2, out, g);
+    const size_t n = 36 * (size_t)g.nc + 1 + (cov == 2 ? 9 * (size_t)g.np : 0);
+    if (rc == ME_OK && hipMemcpyAsync(A->P.host + A->P.cov_off, out.cam, 8 * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+      rc = me_set_error(c, ME_ERR_HIP, "me_ba_solve_async: covariance read-back failed");
+    A->cov = cov;
+  }
   if (rc == ME_OK && hipEventCreateWithFlags(&A->ev, hipEventDisableTiming) != hipSuccess)
     rc = me_set_error(c, ME_ERR_HIP, "me_ba_solve_async: event creation failed");
   if (rc == ME_OK && hipEventRecord(A->ev, c->stream) != hipSuccess) {
@@ -838,6 +881,11 @@ extern "C" int me_ba_solve_async(me_ctx* c, me_ba_problem* p, const me_ba_option
 }
 
 extern "C" int me_ba_wait_out(me_ctx* c, me_ba_summary* s, double* cams, double* pts) {
+  return me_ba_wait_out_cov(c, s, cams, pts, nullptr, nullptr, nullptr);
+}
+
+extern "C" int me_ba_wait_out_cov(me_ctx* c, me_ba_summary* s, double* cams, double* pts, double* cam_cov,
+                                  double* pt_cov, int* cov_ok) {
   me_range range_("me_ba_wait");
   if (!c) return ME_ERR_INVALID;
   auto* Q = (AsyncQueue*)c->ba_async;
@@ -860,6 +908,21 @@ extern "C" int me_ba_wait_out(me_ctx* c, me_ba_summary* s, double* cams, double*
     } else {  // (blocking copies on the null stream: the solve has completed; the ctx stream is not waited)
       if (cams) ME_HIP(c, hipMemcpy(cams, A->prob.cams, 8 * 6 * (size_t)g.nc, hipMemcpyDeviceToHost));
       if (pts && g.np) ME_HIP(c, hipMemcpy(pts, A->prob.pts, 8 * 3 * (size_t)g.np, hipMemcpyDeviceToHost));
+    }
+  }
+  if (cov_ok) {  // the covariance queued behind the solve, from the same staging
+    *cov_ok = 0;
+    if (rc == ME_OK && A->cov) {
+      const Geo& g = A->P.g;
+      const double* h = A->P.host + A->P.cov_off;
+      const size_t ncam = 36 * (size_t)g.nc;
+      int fail[2];
+      std::memcpy(fail, h + ncam, sizeof fail);
+      if (!fail[0] && !fail[1]) {
+        *cov_ok = A->cov;
+        if (cam_cov) std::memcpy(cam_cov, h, 8 * ncam);
+        if (pt_cov && A->cov == 2 && g.np) std::memcpy(pt_cov, h + ncam + 1, 8 * 9 * (size_t)g.np);
+      }
     }
   }
   hipEventDestroy(A->ev);
@@ -908,6 +971,14 @@ extern "C" int me_ba_reserve(me_ctx* c, int n_cams, int n_pts, int n_obs, int ob
     P.reserve_only = true;
     ME_TRY(plan_build(c, &p, &o, P, set, set));
   }
+  {  // the window covariance's set and outputs (me_ba_covariance_full on a device-resident window)
+    Plan P;
+    P.reserve_only = true;
+    P.cov = true;
+    ME_TRY(plan_build(c, &p, &o, P, kCovSet));
+    CovOut out;
+    ME_TRY(cov_out(c, P.g, out));
+  }
   Plan P;  // and the synchronous one
   P.reserve_only = true;
   return plan_build(c, &p, &o, P, 0);
@@ -945,7 +1016,7 @@ extern "C" int me_vo_window_submit(me_ctx* c, const me_vo_window* w, me_ba_probl
   // (the problem's index arrays are the caller's device buffers, filled here)
   ME_TRY(me_ba_window_indices(c, w->frame, w->ids, p->n_obs, w->first_frame, w->win_ids, p->n_pts,
                               const_cast<int32_t*>(p->cam_idx), const_cast<int32_t*>(p->pt_idx)));
-  return solve_async_impl(c, p, o, true);
+  return solve_async_impl(c, p, o, true, w->cov == 1 || w->cov == 2 ? w->cov : 0);
 }
 
 extern "C" void me_ba_default_options(me_ba_options* o) {
@@ -1132,6 +1203,83 @@ extern "C" int me_ba_covariance(me_ctx* c, const me_ba_problem* p, double* cov, 
   ME_HIP(c, hipStreamSynchronize(c->stream));
   *ok = hok;
   if (hok) std::memcpy(cov, h.data(), 8 * h.size());
+  return ME_OK;
+}
+
+// The window covariance of p queued on the ctx stream into the covariance's scratch (out: camera blocks | failure
+// words | landmark blocks when want_pts); the caller takes the blocks from there.  g: the plan's geometry.
+static int cov_enqueue(me_ctx* c, const me_ba_problem* p, bool want_pts, CovOut& out, Geo& gout) {
+  me_ba_options o;
+  me_ba_default_options(&o);
+  o.jacobi_scaling = 0;                      // as me_ba_covariance: S unscaled, no LM damping
+  o.initial_trust_region_radius = INFINITY;
+  Plan P;
+  P.cov = true;
+  const bool dev = p->mem == ME_DEVICE;
+  int rc = plan_build(c, p, &o, P, dev ? kCovSet : 0);
+  if (rc < 0) return rc;
+  P.full_S = true;
+  const Geo& g = P.g;
+  gout = g;
+  ME_CHECK(c, g.n6 <= kCovMaxN, "BA covariance: %d variable cameras exceed the factor's workspace", g.m);
+  ME_TRY(cov_out(c, g, out));
+  hipStream_t s = c->stream;
+  ME_HIP(c, hipMemsetAsync(out.fail, 0, 2 * sizeof(int), s));
+  hipLaunchKernelGGL(cov_prep_kernel, dim3(1), dim3(1), 0, s, P.b);
+  ME_TRY(enqueue_linearize(P));
+  ME_TRY(enqueue_assemble(P));
+  if (g.n6 <= kCovLdsMaxN) {
+    if (!c->ba_cov_lds_attr) {
+      ME_HIP(c, hipFuncSetAttribute((const void*)cov_full_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)cov_lds_bytes(kCovLdsMaxN)));
+      c->ba_cov_lds_attr = 1;
+    }
+    hipLaunchKernelGGL(cov_full_kernel<true>, dim3(1), dim3(kCovFullBlock), cov_lds_bytes(g.n6), s, g, P.b, out.Sig,
+                       out.cam, out.fail);
+  } else {
+    hipLaunchKernelGGL(cov_full_kernel<false>, dim3(1), dim3(kCovFullBlock), 0, s, g, P.b, out.Sig, out.cam, out.fail);
+  }
+  if (want_pts && g.np > 0) {
+    const int nb = blocks(g.np, kCovPtBlock / kCovPtLanes);
+    if (g.od == 4)
+      hipLaunchKernelGGL(cov_points_kernel<4>, dim3(nb), dim3(kCovPtBlock), 0, s, g, P.b, (const double*)out.Sig, P.b.Wo,
+                         out.pt, out.fail);
+    else
+      hipLaunchKernelGGL(cov_points_kernel<2>, dim3(nb), dim3(kCovPtBlock), 0, s, g, P.b, (const double*)out.Sig, P.b.Wo,
+                         out.pt, out.fail);
+  }
+  return me_check_launch(c, "BA covariance");
+}
+
+extern "C" int me_ba_covariance_full(me_ctx* c, const me_ba_problem* p, double* cam_cov, double* pt_cov, int* ok) {
+  me_range range_("me_ba_covariance_full");
+  if (!c || !p || !ok || (!cam_cov && !pt_cov)) return ME_ERR_INVALID;
+  ME_HIP(c, hipSetDevice(c->device));
+  CovOut out;
+  Geo g;
+  ME_TRY(cov_enqueue(c, p, pt_cov != nullptr, out, g));
+  const bool dev = p->mem == ME_DEVICE, pts = pt_cov && g.np > 0;
+  hipStream_t s = c->stream;
+  const long ncam = 36L * g.nc, npt = pts ? 9L * g.np : 0;
+  if (dev) {  // asynchronous: the caller's device arrays and ok word, behind everything queued here
+    hipLaunchKernelGGL(cov_commit_kernel, dim3(blocks(std::max(ncam, npt), kBlock)), dim3(kBlock), 0, s,
+                       (const int*)out.fail, (const double*)out.cam, cam_cov, ncam, (const double*)out.pt, pt_cov, npt,
+                       ok);
+    return me_check_launch(c, "cov_commit_kernel");
+  }
+  void* hp;  // (a larger staging than the plan's: me_pinned waits for the queued input copy before it reallocates)
+  const size_t out_bytes = 8 * (size_t)(ncam + 1 + npt);  // cam | fail | the landmark blocks that were computed
+  ME_TRY(me_pinned(c, out_bytes, &hp));
+  const double* h = (const double*)hp;
+  ME_HIP(c, hipMemcpyAsync(hp, out.cam, out_bytes, hipMemcpyDeviceToHost, s));
+  ME_HIP(c, hipStreamSynchronize(s));
+  int fail[2];
+  std::memcpy(fail, h + ncam, sizeof fail);
+  *ok = !fail[0] && !fail[1];
+  if (*ok) {
+    if (cam_cov) std::memcpy(cam_cov, h, 8 * (size_t)ncam);
+    if (pts) std::memcpy(pt_cov, h + ncam + 1, 8 * (size_t)npt);
+  }
   return ME_OK;
 }
 

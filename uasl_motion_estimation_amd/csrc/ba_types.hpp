@@ -31,6 +31,9 @@
 //                  cost of the point's observations; its last
 //                  workgroup reduces them and runs decide (Ceres LM
 //                  acceptance / radius / termination).
+// Outside the LM iteration (read-only entry points): cost / eval / cov
+// (ba_eval.hpp) and the window covariance, pose and landmark blocks of
+// (J^T J)^-1 from the same linearisation and S (ba_cov.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

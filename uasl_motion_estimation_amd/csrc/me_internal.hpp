@@ -64,6 +64,7 @@ struct me_ctx {
   void* ba_pinned[2] = {nullptr, nullptr};  // staging of the (at most two) queued asynchronous BA solves
   size_t ba_pinned_size[2] = {0, 0};
   int ba_lds_attr = 0;  // dynamic-LDS ceilings of the BA kernels set (plan_build)
+  int ba_cov_lds_attr = 0;  // and of the window covariance's LDS factor (me_ba_covariance_full)
   void* scale_mirror = nullptr;  // coherent host page the scale LM control writes its state to
   int scale_gen = 0;             // generation of the last scale LM solve (mirror ownership)
   int scale_lm_cap = -1;         // co-resident workgroups of the persistent scale LM kernel (-1: not queried)

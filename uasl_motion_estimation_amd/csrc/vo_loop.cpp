@@ -211,6 +211,12 @@ struct me_vo_loop {
   // the rigid-motion gate (me_vo_loop_set_motion_gate, me_hip.h A12h): queued behind the tracked features' matcher
   bool gate = false;
   me_motion_gate_params gate_params{};
+  // the window covariance (me_vo_loop_set_covariance): 0 off, 1 camera blocks, 2 also landmark blocks; per keyframe
+  // the last camera's block of its own window, per live track the block of the latest window that held it
+  // (36 / 9 doubles and the ok word behind them; zeros with ok 0 after a failed solve or covariance)
+  int cov_mode = 0;
+  std::map<int, std::vector<double>> pose_cov;
+  std::map<int64_t, std::vector<double>> track_cov;
   bool klt_predict = false;  // the tracker starts at each landmark's predicted pixel (me_vo_loop_set_klt_predict)
   // ---- keyframe selection (me_vo_loop_set_keyframe_select / me_vo_loop_push, me_hip.h A12i).  Device block
   // "kf" of the kf_n features seeded at the last keyframe: me_vo::Kf (vo_blocks.hpp)
@@ -983,6 +989,7 @@ struct me_vo_loop {
     w.frame = (const int32_t*)(fr + 4 * off0);
     w.ids = (const int32_t*)(id + 4 * off0);
     w.first_frame = f0;
+    w.cov = cov_mode;
     me_ba_problem& p = q->p;
     p = me_ba_problem{};
     p.n_cams = nc;
@@ -1019,7 +1026,9 @@ struct me_vo_loop {
     *n_obs_out = (int)n_obs;
     return ME_OK;
   }
-  int ba_result(std::vector<double>& cams, std::vector<double>& pts, me_ba_summary& s) {
+  // ccov / pcov / cov_ok: the window's covariance, read back with the result (only with the switch on)
+  int ba_result(std::vector<double>& cams, std::vector<double>& pts, me_ba_summary& s,
+                std::vector<double>* ccov = nullptr, std::vector<double>* pcov = nullptr, int* cov_ok = nullptr) {
     if (baq.empty()) return fail(ME_ERR_STATE, "no window solve queued");
     std::unique_ptr<QSolve> q = std::move(baq.front());
     baq.pop_front();
@@ -1029,6 +1038,14 @@ struct me_vo_loop {
     }
     cams.assign(6 * (size_t)q->nc, 0.0);
     pts.assign(3 * (size_t)q->npts, 0.0);
+    if (cov_mode && cov_ok) {
+      ccov->assign(36 * (size_t)q->nc, 0.0);
+      pcov->assign(9 * (size_t)q->npts, 0.0);
+      VL_TRY(timed_wait(4, [&] {
+               return me_ba_wait_out_cov(ctx, &s, cams.data(), pts.data(), ccov->data(), pcov->data(), cov_ok);
+             }), "me_ba_wait_out");
+      return ME_OK;
+    }
     VL_TRY(timed_wait(4, [&] { return me_ba_wait_out(ctx, &s, cams.data(), pts.data()); }), "me_ba_wait_out");
     return ME_OK;
   }
@@ -1098,9 +1115,10 @@ struct me_vo_loop {
       *cost = std::numeric_limits<double>::quiet_NaN();
       return ME_OK;
     }
-    std::vector<double> c, p;
+    std::vector<double> c, p, ccov, pcov;
     me_ba_summary s;
-    VL_TRY(ba_result(c, p, s), "BA result");
+    int cov_ok = 0;
+    VL_TRY(ba_result(c, p, s, &ccov, &pcov, &cov_ok), "BA result");
     const size_t m = ba.upts.size();
     std::vector<int64_t> j(m);
     std::vector<uint8_t> live(m, 1);
@@ -1126,6 +1144,25 @@ struct me_vo_loop {
         if (live[i])
           for (int q = 0; q < 3; ++q) X[3 * j[i] + q] = p[3 * i + q];
     }
+    if (cov_mode) {  // (read only: nothing above depends on it)
+      const bool good = s.status == 2 && cov_ok != 0;
+      std::vector<double> e(37, 0.0);
+      if (good) {
+        std::memcpy(e.data(), &ccov[36 * (size_t)(ba.t - ba.f0)], 36 * sizeof(double));
+        e[36] = 1.0;
+      }
+      pose_cov[ba.t] = e;
+      if (cov_mode == 2)
+        for (size_t i = 0; i < m; ++i) {
+          if (!live[i]) continue;
+          std::vector<double> b(10, 0.0);
+          if (good && cov_ok == 2) {
+            std::memcpy(b.data(), &pcov[9 * i], 9 * sizeof(double));
+            b[9] = 1.0;
+          }
+          track_cov[ba.wids[i]] = b;
+        }
+    }
     *nwp = (int)ba.wids.size();
     *nwo = ba.nobs;
     *iters = s.iterations;
@@ -1150,6 +1187,9 @@ struct me_vo_loop {
       n2 += keep[i];
     }
     if (n2 == ntab()) return;
+    if (cov_mode == 2)
+      for (size_t i = 0; i < ntab(); ++i)
+        if (!keep[i]) track_cov.erase(ids[i]);
     if (cfg.log_events)
       for (size_t i = 0; i < ntab(); ++i)
         if (!keep[i]) events.push_back(me_vo_event{3, -1, ids[i], {0, 0, 0, 0}});
@@ -1691,6 +1731,42 @@ int me_vo_loop_set_klt_predict(me_vo_loop* v, int on) {
   if (started(v, "me_vo_loop_set_klt_predict: guided tracking is set before the first me_vo_loop_process"))
     return ME_ERR_STATE;
   v->klt_predict = on == 1;
+  return ME_OK;
+}
+
+int me_vo_loop_set_covariance(me_vo_loop* v, const me_vo_cov_params* p) {
+  if (!v) return ME_ERR_INVALID;
+  if (started(v, "me_vo_loop_set_covariance: the window covariance is set before the first frame")) return ME_ERR_STATE;
+  v->cov_mode = p ? (p->landmarks ? 2 : 1) : 0;
+  return ME_OK;
+}
+
+int me_vo_loop_pose_covs(me_vo_loop* v, int32_t* ts, double* cov36, uint8_t* ok, int cap, int* n) {
+  if (!v || !n) return ME_ERR_INVALID;
+  *n = (int)v->pose_cov.size();
+  int i = 0;
+  for (auto& kv : v->pose_cov) {
+    if (i >= cap) break;
+    if (ts) ts[i] = kv.first;
+    if (cov36) std::memcpy(cov36 + 36 * (size_t)i, kv.second.data(), 36 * sizeof(double));
+    if (ok) ok[i] = kv.second[36] != 0.0;
+    ++i;
+  }
+  return ME_OK;
+}
+
+int me_vo_loop_track_covs(me_vo_loop* v, int64_t* ids, double* cov9, uint8_t* ok, int cap, int* n) {
+  if (!v || !n) return ME_ERR_INVALID;
+  *n = (int)v->ntab();
+  const int m = std::min(cap, *n);
+  for (int i = 0; i < m; ++i) {
+    const auto it = v->track_cov.find(v->ids[i]);
+    const bool have = it != v->track_cov.end();
+    if (ids) ids[i] = v->ids[i];
+    if (cov9)
+      for (int q = 0; q < 9; ++q) cov9[9 * (size_t)i + q] = have ? it->second[q] : 0.0;
+    if (ok) ok[i] = have && it->second[9] != 0.0;
+  }
   return ME_OK;
 }
 

@@ -636,6 +636,44 @@ class DeviceBAProblem:
         self._async = None
         return _summary(s)
 
+    def covariance_outputs(self, cam_fill: float = 0.0, pt_fill: float = 0.0) -> None:
+        """Create the covariance's device outputs (cov_cam, cov_pt, cov_ok in
+        self.d) if they do not exist, and fill the two block arrays with a
+        value: an ok = 0 result leaves them as they are."""
+        if "cov_cam" not in self.d:
+            sizes = dict(cov_cam=8 * 36 * self.n_cams, cov_pt=8 * 9 * max(self.n_pts, 1), cov_ok=16)
+            for k, n in sizes.items():
+                self.d[k] = self.ctx.malloc(n)
+                self._blocks.append(self.d[k])
+            self.ctx.h2d(self.d["cov_ok"], np.zeros(4, np.int32))
+        self.ctx.h2d(self.d["cov_cam"], np.full(36 * self.n_cams, cam_fill))
+        self.ctx.h2d(self.d["cov_pt"], np.full(9 * max(self.n_pts, 1), pt_fill))
+
+    def covariance_full_async(self, landmarks: bool = True) -> None:
+        """Queue the window covariance of the device-resident cams / pts on
+        the ctx stream (me_ba_covariance_full, ME_DEVICE form): it neither
+        waits for solves queued on the ctx nor shares their scratch.  The
+        device outputs (covariance_outputs) are created on first use."""
+        if "cov_cam" not in self.d:
+            self.covariance_outputs()
+        p = self.struct()
+        self.ctx.check(self.ctx.lib.me_ba_covariance_full(self.ctx.h, byref(p), self.d["cov_cam"],
+                                                          self.d["cov_pt"] if landmarks else None, self.d["cov_ok"]),
+                       "me_ba_covariance_full")
+
+    def covariance_read(self):
+        """(ok, cam_cov, pt_cov) of the last covariance_full_async, as the
+        device holds them (waits for the ctx stream)."""
+        self.ctx.synchronize()
+        ok = np.zeros(1, np.int32)
+        cam = np.zeros((self.n_cams, 6, 6))
+        pt = np.zeros((self.n_pts, 3, 3))
+        self.ctx.d2h(ok, self.d["cov_ok"])
+        self.ctx.d2h(cam, self.d["cov_cam"])
+        if self.n_pts:
+            self.ctx.d2h(pt, self.d["cov_pt"])
+        return int(ok[0]), cam, pt
+
     def download(self):
         cams = np.zeros((self.n_cams, 6))
         pts = np.zeros((self.n_pts, 3))
@@ -897,6 +935,26 @@ def ba_covariance(bp, ctx: Context | None = None):
     return cov.reshape(-1, 6, 6) if ok.value else None
 
 
+def ba_covariance_full(bp, ctx: Context | None = None, landmarks: bool = True):
+    """Window covariance at the problem's current parameters
+    (me_ba_covariance_full): (cam_cov (n_cams, 6, 6), pt_cov (n_pts, 3, 3)) --
+    the pose blocks of ba_covariance and the landmark blocks the reference
+    declares as getPointsCovariance (BundleAdjuster.h:239) -- or None where
+    ba_covariance gives None or a landmark block is not positive definite.
+    ``landmarks=False`` computes the camera blocks only (pt_cov is None)."""
+    ctx = ctx or default_context()
+    keep = []
+    p, _, _ = ba_struct(bp, keep)
+    cam = np.zeros(36 * len(bp.cams))
+    pt = np.zeros(9 * len(bp.pts)) if landmarks else None
+    ok = c_int(0)
+    ctx.check(ctx.lib.me_ba_covariance_full(ctx.h, byref(p), cam.ctypes.data, pt.ctypes.data if landmarks else None,
+                                            ctypes.addressof(ok)), "me_ba_covariance_full")
+    if not ok.value:
+        return None
+    return cam.reshape(-1, 6, 6), (pt.reshape(-1, 3, 3) if landmarks else None)
+
+
 def ba_reduced_system(bp, radius: float = 1e4, ctx: Context | None = None):
     ctx = ctx or default_context()
     keep = []
@@ -940,6 +998,7 @@ class BundleAdjuster:
             raise ValueError("BundleAdjuster<M>: M is 2 (mono) or 4 (stereo)")
         self.M = M
         self.m_camera_covs = []
+        self.m_point_covs = []
         self.calib_params = params
         self.m_status = Status.UNINITIALISED
         self.m_camera_params = []
@@ -1010,19 +1069,25 @@ class BundleAdjuster:
         self.summary = summ
         if self.calib_params.compute_cov:  # BundleAdjuster.h:424-425,471-472
             arrays.cams, arrays.pts = cams, pts
-            cov = ba_covariance(arrays, self.ctx)
-            if cov is None:
+            # one pass for the pose blocks and the landmark blocks the reference declares and leaves empty
+            # (BundleAdjuster.h:277,498-523): both fill, or neither
+            full = ba_covariance_full(arrays, self.ctx)
+            if full is None:
                 print("[Bundle Adjuster] error computing the covariance matrix")
             else:
-                self.m_camera_covs = [c.copy() for c in cov]
+                self.m_camera_covs = [c.copy() for c in full[0]]
+                self.m_point_covs = [c.copy() for c in full[1]]
         self.m_status = Status.SUCCESSFUL if summ["status"] == 2 else Status.FAILED
         return self.m_status
 
     def getPosesCovariance(self):
         return [c.copy() for c in self.m_camera_covs]
 
-    def getPointsCovariance(self):  # never filled by the reference (BundleAdjuster.h:505-506,519-526)
-        return []
+    def getPointsCovariance(self):
+        """3 x 3 blocks per landmark, filled with getPosesCovariance when
+        compute_cov is set (the reference's own computation is commented out,
+        BundleAdjuster.h:505-506,519-526, and returns an empty vector)."""
+        return [c.copy() for c in self.m_point_covs]
 
     def getPoints(self):
         return [p.copy() for p in self.m_point_params]

@@ -133,6 +133,7 @@ class PipelineConfig:
     motion_gate: "MotionGate | None" = None  # motion_gate.MotionGate: tracks that do not move with the camera are dropped
     keyframe_select: "KeyframeSelect | None" = None  # keyframe.KeyframeSelect: push() takes camera frames, picks keyframes
     frame_pose: "FramePose | None" = None  # frame_pose.FramePose: every pushed frame gets a pose relative to the last keyframe
+    covariance: "WindowCovariance | None" = None  # ba_cov.WindowCovariance: every window's covariance (pose_cov / track_cov)
 
     def __post_init__(self):
         if self.keyframe_select is not None:
@@ -151,6 +152,11 @@ class PipelineConfig:
                 raise ValueError("frame_pose needs keyframe_select (push() is what it refines)")
             if not (math.isfinite(self.baseline) and self.baseline > 0.0):
                 raise ValueError("frame_pose: baseline must be finite and > 0")
+        if self.covariance is not None:
+            from .ba_cov import WindowCovariance
+
+            if not isinstance(self.covariance, WindowCovariance):
+                raise ValueError("covariance must be a ba_cov.WindowCovariance or None")
         if self.rectify is not None:
             from .rectify import StereoRectifier
 
@@ -434,6 +440,8 @@ class Backend:
     klt_fb_max = 0.0  # PipelineConfig.klt_fb_max of the loop's configuration (0: no forward-backward check)
     match_lr_max = 0.0  # PipelineConfig.match_lr_max of the loop's configuration (0: no left-right check)
     klt_predict = False  # PipelineConfig.klt_predict of the loop's configuration (True: klt_submit gets a guess)
+    cov_mode = 0  # PipelineConfig.covariance: 0 off, 1 camera blocks, 2 also landmark blocks
+    last_cov = None  # a backend that computes the window covariance itself: (ok, cam_cov, pt_cov) of the last ba_result
     rectifier = None  # PipelineConfig.rectify of the loop's configuration (None: the images come rectified)
     rectifies = False  # True: frame_images takes raw images and warps them itself (on the device)
     equaliser = None  # PipelineConfig.equalise of the loop's configuration (None: the images are used as they come)
@@ -1473,6 +1481,7 @@ class GPUBackend(Backend):
             a.k1, a.k0, a.mode = chain["k1"], chain["k0"], chain["mode"]
         o, f, i = self._wview(self._wcur)
         w.win_ids, w.frame, w.ids, w.first_frame = d + o_ids, f + 4 * off0, i + 4 * off0, f0
+        w.cov = int(self.cov_mode)  # (queued behind the solve, read back with its result: ba_result)
         p = BAProblemC()
         p.n_cams, p.n_pts, p.n_obs = nc, npts, n_obs
         p.cams = ctypes.cast(d, ctypes.POINTER(ctypes.c_double))
@@ -1552,8 +1561,15 @@ class GPUBackend(Backend):
                     self._ba_fut = None
             cams = np.empty((nc, 6), np.float64)
             pts = np.empty((npts, 3), np.float64)
-            c.check(c.lib.me_ba_wait_out(c.h, ctypes.byref(s), cams.ctypes.data_as(ctypes.c_void_p),
-                                         pts.ctypes.data_as(ctypes.c_void_p)), "me_ba_wait_out")
+            if self.cov_mode:  # the window's covariance from the solve's own staging: no further wait
+                ccov, pcov, cok = np.zeros((nc, 6, 6)), np.zeros((npts, 3, 3)), ctypes.c_int(0)
+                c.check(c.lib.me_ba_wait_out_cov(c.h, ctypes.byref(s), cams.ctypes.data, pts.ctypes.data,
+                                                 ccov.ctypes.data, pcov.ctypes.data, ctypes.addressof(cok)),
+                        "me_ba_wait_out")
+                self.last_cov = (cok.value, ccov, pcov)
+            else:
+                c.check(c.lib.me_ba_wait_out(c.h, ctypes.byref(s), cams.ctypes.data_as(ctypes.c_void_p),
+                                             pts.ctypes.data_as(ctypes.c_void_p)), "me_ba_wait_out")
             if self.tlog is not None:
                 import time
 
@@ -1597,6 +1613,9 @@ class WindowedStereoVO:
         self.be.klt_fb_max = float(cfg.klt_fb_max)
         self.be.match_lr_max = float(cfg.match_lr_max)
         self.be.klt_predict = bool(cfg.klt_predict)
+        self.be.cov_mode = 0 if cfg.covariance is None else (2 if cfg.covariance.landmarks else 1)
+        self._pose_cov = {}   # keyframe t -> (ok, 6 x 6): the last camera's block of t's own window
+        self._track_cov = {}  # live track ID -> (ok, 3 x 3): the block of the latest window that held it
         self.be.rectifier = cfg.rectify
         self.be.equaliser = cfg.equalise
         self.be.tonemapper = cfg.tonemap
@@ -2065,7 +2084,8 @@ class WindowedStereoVO:
             return (t, f0, self.ids[upts].copy(), n_obs, upts, self._gen)
         bp = self.ba_problem(t, f0, upts)
         self._wait(self.be.ba_submit, bp, cfg.ba_iters)
-        return (t, f0, self.ids[upts].copy(), len(bp.obs), upts, self._gen)
+        # (with the covariance switch the host problem is kept: its covariance is taken at the solved cams / pts)
+        return (t, f0, self.ids[upts].copy(), len(bp.obs), upts, self._gen) + ((bp,) if self.be.cov_mode else ())
 
     def ba_problem(self, t, f0, upts):
         """The window [f0, t]'s BA problem on the host (host-path backends;
@@ -2099,7 +2119,8 @@ class WindowedStereoVO:
     def _ba_finish(self, ba):
         if ba is None:
             return 0, 0, {"iterations": 0, "final_cost": float("nan")}
-        t, f0, wids, nobs, upts, gen = ba
+        t, f0, wids, nobs, upts, gen = ba[:6]
+        self.be.last_cov = None
         c, p, s = self._wait(self.be.ba_result)
         # the window's tracks now (a pop may have compacted the table since the submit -- its index map;
         # a track popped out of the table, seen only in the window's first keyframe, needs no landmark)
@@ -2124,7 +2145,54 @@ class WindowedStereoVO:
             for k, f in enumerate(range(f0, t + 1)):
                 self.poses[f] = c[k]
             self.X[j[live]] = np.asarray(p)[live]
+        if self.be.cov_mode:  # (read only: nothing above depends on it)
+            self._record_cov(ba, c, p, s, live)
         return len(wids), nobs, s
+
+    def _record_cov(self, ba, c, p, s, live):
+        """The window's covariance beside its result: from the backend when it
+        computed it behind the solve (GPU, device-resident window), else
+        window_cov_ref on this backend's own Jacobians of the host problem at
+        the solved cams / pts.  A failed solve or covariance leaves zeros with
+        ok False."""
+        t, f0, wids = ba[:3]
+        mode = self.be.cov_mode
+        cov = None
+        if s.get("status", 2) == 2:
+            if self.be.last_cov is not None:
+                ok, ccov, pcov = self.be.last_cov
+                cov = (ccov, pcov) if ok else None
+            elif len(ba) > 6:
+                from .ba_cov import stereo_jacobians, window_cov_ref
+
+                bp = ba[6].copy()
+                bp.cams, bp.pts = np.asarray(c, np.float64), np.asarray(p, np.float64)
+                jac = getattr(self.be, "ba_jacobians", stereo_jacobians)
+                r, Jc, Jp = jac(bp)
+                cov = window_cov_ref(r, Jc, Jp, bp.cam_idx, bp.pt_idx, len(bp.cams), len(bp.pts), bp.fixed_frames)
+        self._pose_cov[t] = (True, cov[0][t - f0].copy()) if cov is not None else (False, np.zeros((6, 6)))
+        if mode == 2:
+            for i, tid in enumerate(wids):
+                if live[i]:
+                    self._track_cov[int(tid)] = (True, cov[1][i].copy()) if cov is not None else (False, np.zeros((3, 3)))
+
+    def pose_cov(self, t: int):
+        """6 x 6 covariance of keyframe t's pose {t, angle-axis}: the last
+        camera's block of t's own window, in the BA's gauge (the window's first
+        fixed_frames cameras constant).  None without the switch, for a keyframe
+        without a window of its own or one not completed yet, and after a failed
+        solve or covariance."""
+        e = self._pose_cov.get(int(t))
+        return e[1].copy() if e is not None and e[0] else None
+
+    def pose_cov_ok(self) -> dict:
+        """Keyframe -> whether its window's covariance was obtained (every keyframe that had a window)."""
+        return {t: bool(e[0]) for t, e in self._pose_cov.items()}
+
+    def track_cov(self) -> dict:
+        """Live track ID -> 3 x 3 covariance of its landmark, from the latest
+        window that held it (tracks whose latest window failed are left out)."""
+        return {tid: e[1].copy() for tid, e in self._track_cov.items() if e[0]}
 
     def _pop(self, new_first):
         """WBA_Point::pop() of every feature older than `new_first`; empty tracks deleted."""
@@ -2140,6 +2208,8 @@ class WindowedStereoVO:
         if dead.any():
             if self.log_events:
                 self._ev.append(("del", self.ids[np.flatnonzero(dead)].copy()))
+            for tid in self.ids[np.flatnonzero(dead)] if self._track_cov else ():
+                self._track_cov.pop(int(tid), None)
             keep = ~dead  # (the observation store holds IDs: nothing to re-index)
             n2 = int(keep.sum())
             k = 1 - self._tcur
@@ -2236,6 +2306,11 @@ class NativeStereoVO:
                 self._check(self.lib.me_vo_loop_set_motion_gate(self.h, ctypes.byref(gp)), "me_vo_loop_set_motion_gate")
             if cfg.klt_predict:
                 self._check(self.lib.me_vo_loop_set_klt_predict(self.h, 1), "me_vo_loop_set_klt_predict")
+            if cfg.covariance is not None:
+                from ._lib import VOCovParamsC
+
+                cp = VOCovParamsC(int(bool(cfg.covariance.landmarks)))
+                self._check(self.lib.me_vo_loop_set_covariance(self.h, ctypes.byref(cp)), "me_vo_loop_set_covariance")
             if cfg.keyframe_select is not None:
                 kc = cfg.keyframe_select.to_c()
                 self._check(self.lib.me_vo_loop_set_keyframe_select(self.h, ctypes.byref(kc)),
@@ -2504,6 +2579,39 @@ class NativeStereoVO:
         self._check(self.lib.me_vo_loop_poses(self.h, ts.ctypes.data, ps.ctypes.data, n.value, ctypes.byref(n)),
                     "poses")
         return {int(t): ps[i] for i, t in enumerate(ts)}
+
+    def _pose_covs(self):
+        import ctypes
+
+        n = ctypes.c_int()
+        self._check(self.lib.me_vo_loop_pose_covs(self.h, None, None, None, 0, ctypes.byref(n)), "pose_covs")
+        m = n.value
+        ts, cov, ok = np.zeros(m, np.int32), np.zeros((m, 6, 6)), np.zeros(m, np.uint8)
+        self._check(self.lib.me_vo_loop_pose_covs(self.h, ts.ctypes.data, cov.ctypes.data, ok.ctypes.data, m,
+                                                  ctypes.byref(n)), "pose_covs")
+        return ts, cov, ok.astype(bool)
+
+    def pose_cov(self, t: int):
+        """WindowedStereoVO.pose_cov (me_vo_loop_pose_covs)."""
+        ts, cov, ok = self._pose_covs()
+        k = np.flatnonzero(ts == int(t))
+        return cov[k[0]].copy() if len(k) and ok[k[0]] else None
+
+    def pose_cov_ok(self) -> dict:
+        ts, _, ok = self._pose_covs()
+        return {int(t): bool(o) for t, o in zip(ts, ok)}
+
+    def track_cov(self) -> dict:
+        """WindowedStereoVO.track_cov (me_vo_loop_track_covs)."""
+        import ctypes
+
+        n = ctypes.c_int()
+        self._check(self.lib.me_vo_loop_track_covs(self.h, None, None, None, 0, ctypes.byref(n)), "track_covs")
+        m = n.value
+        ids, cov, ok = np.zeros(m, np.int64), np.zeros((m, 3, 3)), np.zeros(m, np.uint8)
+        self._check(self.lib.me_vo_loop_track_covs(self.h, ids.ctypes.data, cov.ctypes.data, ok.ctypes.data, m,
+                                                   ctypes.byref(n)), "track_covs")
+        return {int(i): cov[k].copy() for k, i in enumerate(ids) if ok[k]}
 
     @property
     def obs(self) -> dict:
