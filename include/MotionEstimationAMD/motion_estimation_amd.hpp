@@ -981,7 +981,7 @@ inline std::vector<uint8_t> tonemap16(const ImageView16& img, const ToneMapParam
 }
 }  // namespace amd
 
-// The windowed stereo VO loop (me_vo_loop_*, csrc/vo_loop.hip): the
+// The windowed stereo VO loop (me_vo_loop_*, csrc/vo_loop.cpp): the
 // application loop the reference leaves to its caller -- per keyframe KLT,
 // epipolar MI matching, WBA_Point bookkeeping (feature_types.h:121-197),
 // scale LM (Optimiser<ScaleState,...>) and the sliding-window

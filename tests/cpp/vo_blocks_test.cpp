@@ -70,6 +70,22 @@ void layouts(size_t n) {
     CHECK(off(k.pose_block(b)) == 16 * ((30 * n + 15) / 16) + 32);
     CHECK(k.size() == 16 * ((30 * n + 15) / 16) + 160);
   }
+  {  // the window store of capacity n, element e (wview and the compaction / per-frame copies of window_add)
+    const me_vo::WStore w{n};
+    const size_t cap = n;
+    CHECK(w.size() == 40 * cap && w.o_frame() == 32 * cap && w.o_id() == 36 * cap);
+    CHECK(off(w.obs(b)) == 0 && off(w.frame(b)) == 32 * cap && off(w.id(b)) == 36 * cap);
+    for (size_t e : {(size_t)0, n / 2, n})
+      CHECK(off(w.obs(b, e)) == 32 * e && off(w.frame(b, e)) == 32 * cap + 4 * e && off(w.id(b, e)) == 36 * cap + 4 * e);
+  }
+  for (size_t nc : {(size_t)1, (size_t)3, (size_t)50}) {  // the BA upload block of nc cameras and n points
+    const me_vo::BaUpload u{nc, n};
+    const size_t npts = n, o_ids = 48 * nc + 24 * npts, o_cs = o_ids + 4 * npts, nb = o_cs + 4 * nc;
+    CHECK(off(u.cams(b)) == 0 && off(u.pts(b)) == 48 * nc && off(u.ids(b)) == o_ids && off(u.cam_src(b)) == o_cs);
+    CHECK(u.o_pts() == 48 * nc && u.o_ids() == o_ids && u.o_cam_src() == o_cs && u.size() == nb);
+    CHECK(u.size() == 48 * nc + 24 * npts + 4 * npts + 4 * nc);  // (reserve)
+    CHECK(u.stage_bytes(true) == nb && u.stage_bytes(false) == o_cs);
+  }
 }
 
 // The host decode of the new-feature block: the first count features, the count clamped to [0, m]

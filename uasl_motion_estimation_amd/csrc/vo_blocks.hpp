@@ -106,6 +106,34 @@ struct Kf {
   uint8_t* pose_block(void* b) const { return at<uint8_t>(b, o_pose()); }
 };
 
+// The device-resident BA window store of capacity cap observations, frame by frame: obs (4 doubles, 32 cap) |
+// frame (int32, 4 cap) | track ID (int32, 4 cap).  The same layout with cap = n is a frame's page-locked staging
+// block "w_add", copied part by part to element e of the store.
+struct WStore {
+  size_t cap;
+  size_t o_frame() const { return 32 * cap; }
+  size_t o_id() const { return 36 * cap; }
+  size_t size() const { return 40 * cap; }
+  double* obs(void* b, size_t e = 0) const { return at<double>(b, 32 * e); }
+  int32_t* frame(void* b, size_t e = 0) const { return at<int32_t>(b, o_frame() + 4 * e); }
+  int32_t* id(void* b, size_t e = 0) const { return at<int32_t>(b, o_id() + 4 * e); }
+};
+
+// "bw": a window solve's upload.  cams (6 doubles, 48 nc) | pts (3 doubles, 24 npts) | ids (int32, 4 npts) |
+// cam_src (int32, 4 nc; chained solves only: the copy stops ahead of it otherwise)
+struct BaUpload {
+  size_t nc, npts;
+  size_t o_pts() const { return 48 * nc; }
+  size_t o_ids() const { return 48 * nc + 24 * npts; }
+  size_t o_cam_src() const { return o_ids() + 4 * npts; }
+  size_t size() const { return o_cam_src() + 4 * nc; }
+  size_t stage_bytes(bool chained) const { return chained ? size() : o_cam_src(); }
+  double* cams(void* b) const { return at<double>(b, 0); }
+  double* pts(void* b) const { return at<double>(b, o_pts()); }
+  int32_t* ids(void* b) const { return at<int32_t>(b, o_ids()); }
+  int32_t* cam_src(void* b) const { return at<int32_t>(b, o_cam_src()); }
+};
+
 // The pair pool's rule: a frame's 8-bit pair goes into the lowest slot held neither by the previous pushed frame
 // (prev; -1: that frame was a keyframe) nor by either of the last two keyframes (-1: none yet).  A keyframe's pair
 // is read during its call and the next one, and by the scale LM queued in the call after.  Three held at the most,

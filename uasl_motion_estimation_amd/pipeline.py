@@ -2247,7 +2247,7 @@ def synthetic_sequence(c: int, n_frames: int, seed: int | None = None, render_di
 
 class NativeStereoVO:
     """The windowed stereo VO loop of WindowedStereoVO with the GPU backend,
-    every step in native code behind the C ABI (me_vo_loop_*, csrc/vo_loop.hip):
+    every step in native code behind the C ABI (me_vo_loop_*, csrc/vo_loop.cpp and its vo_*.hpp parts):
     the Python layer only hands images in and reads results out.  Same
     decisions, events, results and poses as WindowedStereoVO(GPUBackend)
     (tests/test_pipeline.py, test_native_loop_*).  Two contexts of the device as GPUBackend sets
