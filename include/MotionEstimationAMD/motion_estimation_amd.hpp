@@ -1234,6 +1234,34 @@ class WindowedStereoVO {
     ok.resize((size_t)n);
     check(me_vo_loop_track_covs(v_.get(), ids.data(), n ? cov[0].data() : nullptr, ok.data(), n, &n), "track_cov");
   }
+  // The residual check behind every window solve (me_vo_loop_set_track_check,
+  // me_ba_point_check's rule): a track whose largest per-observation chi2 in
+  // its solved window exceeds chi2_max, or that lies at a depth <= z_min in
+  // some camera, is tracked no further.  Off by default; before the first
+  // frame, a later call throws.  The defaults (18.47, the 99.9 % point of
+  // chi-square with 4 degrees of freedom, and 0) come from the statistics, not
+  // from real data.
+  void setTrackCheck(bool on, double chi2_max = 18.47, double z_min = 0.0) {
+    const me_ba_point_check_params p{chi2_max, z_min};
+    check(me_vo_loop_set_track_check(v_.get(), on ? &p : nullptr), "WindowedStereoVO::setTrackCheck");
+  }
+  struct Flagged {
+    int t;          // the window's keyframe
+    int64_t id;     // the track
+    uint8_t flags;  // 1: chi2 above the bound, 2: behind a camera
+  };
+  // every track the check dropped so far, in the order applied
+  std::vector<Flagged> flagged() const {
+    int n = 0;
+    check(me_vo_loop_flagged(v_.get(), nullptr, nullptr, nullptr, 0, &n), "flagged");
+    std::vector<int32_t> ts((size_t)n);
+    std::vector<int64_t> ids((size_t)n);
+    std::vector<uint8_t> fl((size_t)n);
+    check(me_vo_loop_flagged(v_.get(), ts.data(), ids.data(), fl.data(), n, &n), "flagged");
+    std::vector<Flagged> out;
+    for (int i = 0; i < n; ++i) out.push_back(Flagged{ts[i], ids[i], fl[i]});
+    return out;
+  }
 
  private:
   void check(int rc, const char* what) const {

@@ -96,7 +96,7 @@ int me_host_free(me_ctx* ctx, void* hptr);
 enum { ME_KT_MI = 0, ME_KT_SCALE_RES = 1, ME_KT_SCALE_NEQ = 2, ME_KT_BA_LINEARIZE = 3, ME_KT_BA_POINTS = 4,
        ME_KT_BA_SCHUR = 5, ME_KT_BA_SOLVE = 6, ME_KT_BA_STEP = 7, ME_KT_KLT = 8, ME_KT_PYR = 9, ME_KT_NMS = 10,
        ME_KT_CORNERS = 11, ME_KT_RECTIFY = 12, ME_KT_CLAHE = 13, ME_KT_TONEMAP = 14, ME_KT_GATE = 15,
-       ME_KT_KEYFRAME = 16, ME_KT_FRAMEPOSE = 17, ME_KT_COUNT = 18, ME_KT_ALL = 0x3ffff };
+       ME_KT_KEYFRAME = 16, ME_KT_FRAMEPOSE = 17, ME_KT_BA_CHECK = 18, ME_KT_COUNT = 19, ME_KT_ALL = 0x7ffff };
 int me_timing_enable(me_ctx* ctx, int family_mask);
 int me_timing_read(me_ctx* ctx, int kernel, long* launches, double* total_ms);
 int me_timing_reset(me_ctx* ctx);
@@ -386,9 +386,18 @@ int me_ba_wait_out(me_ctx* ctx, me_ba_summary* s, double* cams, double* pts);
    of the three may be NULL. */
 int me_ba_wait_out_cov(me_ctx* ctx, me_ba_summary* s, double* cams, double* pts, double* cam_cov, double* pt_cov,
                        int* cov_ok);
+/* me_ba_wait_out_cov, and the flags of the residual check that
+   me_vo_window_submit queued behind the solve (me_vo_window.check), from the
+   same staging and with no further wait: flags (n_pts bytes) and
+   *check_ok = 1.  *check_ok = 0 with flags untouched when none was queued,
+   the solve failed (termination 2) or the wait failed.  flags and check_ok
+   may be NULL.  me_ba_wait, me_ba_wait_out and me_ba_wait_out_cov are this
+   call with the outputs they lack NULL. */
+int me_ba_wait_out_check(me_ctx* ctx, me_ba_summary* s, double* cams, double* pts, double* cam_cov, double* pt_cov,
+                         int* cov_ok, uint8_t* flags, int* check_ok);
 /* Sizes the ctx's BA scratch and page-locked staging (synchronous, both
-   asynchronous sets and the window covariance's set, me_ba_covariance_full)
-   for windows up to these sizes, so a growing window does
+   asynchronous sets, the window covariance's set, me_ba_covariance_full, and
+   the residual check's flags, me_ba_point_check) for windows up to these sizes, so a growing window does
    not reallocate (a reallocation waits for the ctx stream).  No solve may be
    queued. */
 int me_ba_reserve(me_ctx* ctx, int n_cams, int n_pts, int n_obs, int obs_dim, int fixed_frames);
@@ -417,6 +426,40 @@ typedef struct me_vo_chain_args {
 int me_vo_ba_chain(me_ctx* ctx, double* cams, int n_cams, double* pts, int n_pts, const int32_t* cam_src,
                    const int32_t* win_ids, const int32_t* prev_ids, int n_prev, int32_t new_from,
                    const me_vo_chain_args* a);
+/* Per-landmark residual check of a BA problem at its current parameters
+   (build-defined: the reference has no counterpart).  Read
+   only.  Per observation o, with the sigma-scaled residual r of me_ba_evaluate
+   (rows 2, 3 zero for obs_dim 2) and the camera-frame depth Z_o (the third
+   coordinate of R X + t):
+     s_o = ((r0 r0 + r1 r1) + r2 r2) + r3 r3      (FP64, no contraction: the
+                                                   BA cost's sum without the
+                                                   Huber correction)
+   Per landmark i over all of its observations, constant cameras included:
+     chi2[i]  = max s_o; a non-finite s_o counts as +inf; no observation: 0
+     flags[i] bit 0 (1): !(chi2[i] <= chi2_max)
+              bit 1 (2): some observation has !(Z_o > z_min)
+   so a NaN landmark sets both bits.  A maximum and an "any": the result does
+   not depend on the order of the observation arrays, bit for bit.
+   Defaults (me_ba_point_check_default_params): chi2_max = 18.47, the 99.9 %
+   point of chi-square with 4 degrees of freedom, and z_min = 0 -- both from
+   the statistics of a 4-row residual with the stated sigma, not tuned on real
+   data.  chi2_max must be > 0 (+inf allowed), z_min finite and >= 0; NaN is
+   ME_ERR_INVALID.  params NULL: the defaults.
+   ME_HOST problems: host outputs, chi2 (n_pts, may be NULL), flags (n_pts),
+   *n_flagged (may be NULL) = landmarks with flags != 0; the call returns with
+   them.  ME_DEVICE problems: chi2 / flags are device pointers, n_flagged must
+   be NULL and the call is asynchronous on the ctx stream; like
+   me_ba_covariance_full it does not wait for solves queued on the ctx and
+   works in that call's scratch set (me_ba_reserve sizes it).  A
+   device-resident problem whose observations index outside the window gets
+   +inf and both bits everywhere.  One launch, timed as ME_KT_BA_CHECK. */
+typedef struct me_ba_point_check_params {
+  double chi2_max;
+  double z_min;
+} me_ba_point_check_params;
+void me_ba_point_check_default_params(me_ba_point_check_params* p);
+int me_ba_point_check(me_ctx* ctx, const me_ba_problem* p, const me_ba_point_check_params* params,
+                      double* chi2 /* n_pts or NULL */, uint8_t* flags /* n_pts */, int* n_flagged);
 /* One keyframe's window solve in one call (for a thread that queues window t
    while another waits for window t-1 with me_ba_wait_out -- the two may run
    concurrently on one ctx; no other call on the ctx meanwhile): the staged
@@ -441,6 +484,9 @@ typedef struct me_vo_window {
   int cov; /* 0: none.  1 / 2: the window covariance (camera blocks / also landmark blocks, me_ba_covariance_full)
               queued directly behind the solve on the ctx stream, in scratch of its own, read back into the solve's
               staging ahead of its event: me_ba_wait_out_cov returns it with the solve's result, no further wait */
+  const me_ba_point_check_params* check; /* NULL: none.  Else me_ba_point_check at the cams / pts the solve leaves,
+              launched directly behind the solve (behind the covariance when both are asked for); its flags (n_pts
+              bytes) go into the solve's staging ahead of its event: me_ba_wait_out_check returns them */
 } me_vo_window;
 int me_vo_window_submit(me_ctx* ctx, const me_vo_window* w, me_ba_problem* p, const me_ba_options* o);
 /* ---- the windowed stereo VO loop, native (round 5) ----------------------
@@ -533,6 +579,22 @@ typedef struct me_vo_cov_params {
 int me_vo_loop_set_covariance(me_vo_loop* v, const me_vo_cov_params* p);
 int me_vo_loop_pose_covs(me_vo_loop* v, int32_t* ts, double* cov36, uint8_t* ok, int cap, int* n);
 int me_vo_loop_track_covs(me_vo_loop* v, int64_t* ids, double* cov9, uint8_t* ok, int cap, int* n);
+/* Residual check behind every window solve (NULL: off, the default; set
+   before the first frame; parameters as me_ba_point_check, else
+   ME_ERR_INVALID).  Every window's check is queued with its solve
+   (me_vo_window.check) and read back with its result: no extra host wait.
+   When window t-1's result is applied (step 7 of keyframe t), every live
+   track of that window with flags != 0 is made inactive: it keeps the
+   observations it has (keyframe t's included: BA(t) may already be queued),
+   is tracked no further from keyframe t+1 on, frees its cell for a new
+   feature and leaves the window by the ordinary pops.  A failed solve
+   (termination 2) applies no flags.  No event kind is added; independent of
+   the covariance, motion gate, keyframe selection and frame pose switches.
+   me_vo_loop_flagged: every (window keyframe, track ID, flags) applied so far,
+   in the order applied (window by window, table order inside one); *n =
+   entries, at most cap written; outputs may be NULL. */
+int me_vo_loop_set_track_check(me_vo_loop* v, const me_ba_point_check_params* p /* NULL: off */);
+int me_vo_loop_flagged(me_vo_loop* v, int32_t* ts, int64_t* ids, uint8_t* flags, int cap, int* n);
 /* Rectification inside the loop (A12d): with two camera models the loop builds
    their maps once on the front context -- the rectified model is the loop's
    own width, height and K (fx = K[0], fy = K[4], cx = K[2], cy = K[5]) -- and

@@ -56,6 +56,10 @@ loads another build of libme_hip.so (tools/build_variant.sh).
                          per call, and the config-3 native loop with the covariance switch off / cameras /
                          cameras and landmarks, alternating.  --trace 1: the calls alone (under rocprofv3
                          --kernel-trace --stats)
+  track_check [--repeats --loop N --kernel-time 0|1]
+                         the config-3 native loop over N keyframes with the residual check behind every window
+                         solve off / on, alternating, same build: keyframes/s, the ME_KT_BA_CHECK time per launch
+                         and the tracks flagged
 """
 import argparse
 import ctypes
@@ -1640,6 +1644,56 @@ def cmd_window_cov(a):
                                       "windows_ok": int(sum(okc.values())), "windows": len(okc)}), flush=True)
 
 
+def cmd_track_check(a):
+    """The config-3 native loop with and without the residual check behind every window solve
+    (PipelineConfig(track_check=TrackCheck())), same build, the two interleaved: keyframes/s, the ME_KT_BA_CHECK
+    time per launch (event timing of that family alone, on the BA context) and the number of tracks flagged."""
+    import torch
+
+    from uasl_motion_estimation_amd import pipeline as PL
+    from uasl_motion_estimation_amd import synthetic as S
+    from uasl_motion_estimation_amd.track_check import TrackCheck
+    ctx = _setup(a.lib)
+    NK = a.loop
+    arc = S.trajectory_arc(max(NK, 2))
+    truth = [np.concatenate([t, S.R_to_aa_robust(R)]) for (R, t) in arc]
+    K = S.intrinsics(1280, 720)
+    frames = []
+    for c0 in range(0, NK, 50):
+        _, fr = S.corridor_frames_torch(S.SEED0 + 3, 1280, 720, c0, min(50, NK - c0))
+        frames += [(Lk.contiguous(), Rk.contiguous()) for (Lk, Rk, _, _) in fr]
+        torch.cuda.synchronize()
+    for rep_ in range(-1, a.repeats):  # (-1: a short untimed run, the first loop of a process pays the allocations)
+        for name, chk in (("off", None), ("on", TrackCheck())):
+            timed = a.kernel_time and rep_ >= 0
+            if timed:
+                ctx.timing(True, ["BA_CHECK"])
+                ctx.timing_sample(1)
+                ctx.timing_reset()
+            cfg = PL.PipelineConfig.from_config(3, track_check=chk)
+            vo = PL.NativeStereoVO(cfg, ctx, K, truth[0], truth[1] - truth[0], log_events=False, overlap=True)
+            t0 = time.perf_counter()
+            for t in range(NK if rep_ >= 0 else min(NK, 30)):
+                vo.process(t, *frames[t])
+            vo.finish()
+            dt = time.perf_counter() - t0
+            fl = vo.flagged()
+            n_active = [r.n_active for r in vo.results]
+            vo.close()
+            launches, ms = (0, 0.0)
+            if timed:
+                ctx.synchronize()
+                launches, ms = ctx.timing_read("BA_CHECK")
+                ctx.timing(False)
+            if rep_ >= 0:
+                print(json.dumps({"track_check": name, "repeat": rep_, "keyframes": NK,
+                                  "keyframes_per_s": round(NK / dt, 2), "us_per_keyframe": round(1e6 * dt / NK, 1),
+                                  "check_launches": launches,
+                                  "check_us_per_launch": round(1e3 * ms / launches, 2) if launches else None,
+                                  "flag_entries": len(fl), "tracks_flagged": len({i for _, i, _ in fl}),
+                                  "mean_n_active": round(float(np.mean(n_active)), 1)}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--lib", default=os.environ.get("ME_LIB"))
@@ -1720,6 +1774,11 @@ def main():
     p.add_argument("--repeats", type=int, default=3)
     p.add_argument("--trace", type=int, default=0, help="1: the calls alone, nothing timed (under rocprofv3)")
     p.add_argument("--loop", type=int, default=200, help="keyframes of the config-3 native loop per run (0: skip)")
+    p = sub.add_parser("track_check")
+    p.add_argument("--repeats", type=int, default=3)
+    p.add_argument("--loop", type=int, default=200, help="keyframes of the config-3 native loop per run")
+    p.add_argument("--kernel-time", dest="kernel_time", type=int, default=1,
+                   help="1: event timing of ME_KT_BA_CHECK (two event records per window on the BA stream); 0: none")
     a = ap.parse_args()
     globals()["cmd_" + a.cmd](a)
 

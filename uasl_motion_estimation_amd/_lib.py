@@ -39,7 +39,7 @@ ERRORS = {
 KT = dict(MI=0, SCALE_RES=1, SCALE_NEQ=2, BA_LINEARIZE=3, BA_POINTS=4, BA_SCHUR=5, BA_SOLVE=6, BA_STEP=7,
           KLT=8, PYR=9, NMS=10, CORNERS=11, RECTIFY=12, CLAHE=13, TONEMAP=14, GATE=15)
 # families from 16 on (tests/test_rectify.py pins KT's values below 16): timing() / timing_read() take these names too
-KT_MORE = dict(KEYFRAME=16, FRAMEPOSE=17)
+KT_MORE = dict(KEYFRAME=16, FRAMEPOSE=17, BA_CHECK=18)
 
 
 class MEError(RuntimeError):
@@ -119,7 +119,12 @@ class VOWindowC(ctypes.Structure):
     _fields_ = [("stage", c_void_p), ("dev", c_void_p), ("stage_bytes", c_size_t), ("chain", c_int),
                 ("cam_src", c_void_p), ("win_ids", c_void_p), ("prev_ids", c_void_p), ("n_prev", c_int),
                 ("new_from", ctypes.c_int32), ("args", VOChainArgsC), ("frame", c_void_p), ("ids", c_void_p),
-                ("first_frame", c_int), ("cov", c_int)]
+                ("first_frame", c_int), ("cov", c_int), ("check", c_void_p)]
+
+
+class PointCheckParamsC(ctypes.Structure):
+    """me_ba_point_check_params (include/me_hip.h)."""
+    _fields_ = [("chi2_max", c_double), ("z_min", c_double)]
 
 
 class VOCovParamsC(ctypes.Structure):
@@ -235,6 +240,8 @@ EXPORTS = [
     "me_motion_gate_default_params", "me_motion_gate", "me_vo_loop_set_motion_gate",
     "me_vo_loop_set_klt_predict", "me_vo_loop_set_covariance", "me_vo_loop_pose_covs", "me_vo_loop_track_covs",
     "me_ba_wait_out_cov",
+    "me_ba_point_check_default_params", "me_ba_point_check", "me_ba_wait_out_check", "me_vo_loop_set_track_check",
+    "me_vo_loop_flagged",
     "me_kf_default_params", "me_kf_update", "me_vo_loop_set_keyframe_select", "me_vo_loop_push",
     "me_frame_pose_default_params", "me_frame_pose", "me_vo_loop_set_frame_pose", "me_vo_loop_frame_poses",
 ]
@@ -371,6 +378,12 @@ def load_library(path: str | None = None):
         "me_vo_loop_pose_covs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, P(c_int)]),
         "me_vo_loop_track_covs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, P(c_int)]),
         "me_ba_wait_out_cov": (c_int, [c_void_p, P(BASummaryC), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+        "me_ba_wait_out_check": (c_int, [c_void_p, P(BASummaryC), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p]),
+        "me_ba_point_check_default_params": (None, [P(PointCheckParamsC)]),
+        "me_ba_point_check": (c_int, [c_void_p, P(BAProblemC), P(PointCheckParamsC), c_void_p, c_void_p, c_void_p]),
+        "me_vo_loop_set_track_check": (c_int, [c_void_p, c_void_p]),
+        "me_vo_loop_flagged": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, P(c_int)]),
         "me_vo_loop_last_error": (ctypes.c_char_p, [c_void_p]),
         "me_vo_loop_process": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int]),
         "me_vo_loop_finish": (c_int, [c_void_p]),
@@ -574,7 +587,7 @@ class Context:
         """Enable HIP-event timing of every kernel family, or only of `families` (names of KT)."""
         mask = 0
         if on:
-            mask = 0x3FFFF if families is None else sum(1 << {**KT, **KT_MORE}[f] for f in families)
+            mask = 0x7FFFF if families is None else sum(1 << {**KT, **KT_MORE}[f] for f in families)
         self.check(self.lib.me_timing_enable(self.h, mask))
 
     def timing_sample(self, every: int):

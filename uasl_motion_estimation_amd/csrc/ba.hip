@@ -91,6 +91,8 @@ struct Plan {
   size_t cov_off = 0;       // asynchronous plans: where the staging holds a covariance queued behind the solve (doubles)
   bool cov = false;         // me_ba_covariance_full: a device-resident problem's plan queues behind the asynchronous
                             // solves (no drain) and takes no host staging
+  size_t check_off = 0;     // asynchronous plans: where the staging holds the flags of a residual check queued behind
+                            // the solve (bytes; behind the covariance's part)
   int solve_cap = 0;        // co-resident cam_solve_kernel<2> workgroups on the ctx's CUs (0: not queried)
   me_comm* comm = nullptr;  // sharded solve: the exchange (null: one GPU)
   bool xmax_separate = false;  // ABI-v2 callback (no rank): the gradient max-norm travels in its own max all-reduce
@@ -350,7 +352,10 @@ int plan_build(me_ctx* c, const me_ba_problem* p, const me_ba_options* opt, Plan
   // (an asynchronous solve's staging also takes the window covariance queued behind it: cam | fail | pt blocks)
   const size_t cov_doubles = async >= 0 ? 36 * (size_t)g.nc + 1 + 9 * (size_t)g.np : 0;
   P.cov_off = out_doubles;
-  const size_t stage = rup((long)std::max(8 * (out_doubles + cov_doubles), dev ? (size_t)0 : input_span), 64);
+  // (and the flags of the residual check queued behind it: one byte per landmark)
+  const size_t check_bytes = async >= 0 ? (size_t)rup(g.np, 8) : 0;
+  P.check_off = 8 * (out_doubles + cov_doubles);
+  const size_t stage = rup((long)std::max(P.check_off + check_bytes, dev ? (size_t)0 : input_span), 64);
   const size_t hbytes = stage + 2 * rup(sizeof(State), 64);
   if (async >= 0) {  // staging owned by the asynchronous solve (set `async` is free: its last solve was waited)
     if (c->ba_pinned_size[async] < hbytes) {
@@ -730,6 +735,7 @@ struct AsyncSolve {
   bool completed = false;
   int rc = ME_OK;
   int cov = 0;  // window covariance queued behind the solve (solve_async_impl): staged at P.host + P.cov_off
+  bool check = false;  // residual check queued behind the solve: its flags staged at P.host (bytes) + P.check_off
   me_ba_summary sum{};
 };
 constexpr int kBaQueue = 2;
@@ -798,6 +804,10 @@ AsyncSolve* ba_chain_source(AsyncQueue* Q) {
 // blocks: a host problem reads back from the camera blocks on, up to the
 // failure words when no landmark block was asked for.
 constexpr int kCovSet = 2, kCovOutSlot = SLOT_COUNT + 3;
+// The residual check's outputs where the caller gives no device memory (a host problem's chi2 | flags, the flags
+// of a check queued behind a solve): one slot, used in stream order.  A device-resident problem's stand-alone check
+// builds its plan in the covariance's set.
+constexpr int kCheckOutSlot = SLOT_COUNT + 4;
 struct CovOut {
   double *Sig, *cam, *pt;
   int* fail;
@@ -822,7 +832,10 @@ static int cov_enqueue(me_ctx* c, const me_ba_problem* p, bool want_pts, CovOut&
 
 // cov: 0 none, 1 the window covariance's camera blocks, 2 also its landmark blocks, queued behind the solve's
 // output at the cams / pts it leaves and read back into the solve's staging (me_ba_wait_out_cov) ahead of its event
-static int solve_async_impl(me_ctx* c, me_ba_problem* p, const me_ba_options* opt, bool copy_out, int cov = 0) {
+// check: the residual check (me_ba_point_check) behind both, over the solve's own plan (its CSR by point is intact
+// until the set is built again), its flags read back the same way (me_ba_wait_out_check)
+static int solve_async_impl(me_ctx* c, me_ba_problem* p, const me_ba_options* opt, bool copy_out, int cov = 0,
+                            const me_ba_point_check_params* check = nullptr) {
   if (!c || !p || !opt) return ME_ERR_INVALID;
   ME_HIP(c, hipSetDevice(c->device));
   AsyncQueue* Q = ba_queue(c);
@@ -853,6 +866,16 @@ static int solve_async_impl(me_ctx* c, me_ba_problem* p, const me_ba_options* op
     if (rc == ME_OK && hipMemcpyAsync(A->P.host + A->P.cov_off, out.cam, 8 * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
       rc = me_set_error(c, ME_ERR_HIP, "me_ba_solve_async: covariance read-back failed");
     A->cov = cov;
+  }
+  if (rc == ME_OK && check && A->P.dev) {
+    const Geo& g = A->P.g;
+    void* d = nullptr;
+    rc = me_scratch(c, kCheckOutSlot, (size_t)std::max(g.np, 1), &d);
+    if (rc == ME_OK) rc = me_ba_check_launch(c, g, A->P.b, A->prob.cams, A->prob.pts, check, nullptr, (uint8_t*)d);
+    if (rc == ME_OK && g.np &&
+        hipMemcpyAsync((char*)A->P.host + A->P.check_off, d, (size_t)g.np, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+      rc = me_set_error(c, ME_ERR_HIP, "me_ba_solve_async: residual check read-back failed");
+    A->check = true;
   }
   if (rc == ME_OK && hipEventCreateWithFlags(&A->ev, hipEventDisableTiming) != hipSuccess)
     rc = me_set_error(c, ME_ERR_HIP, "me_ba_solve_async: event creation failed");
@@ -886,7 +909,13 @@ extern "C" int me_ba_wait_out(me_ctx* c, me_ba_summary* s, double* cams, double*
 
 extern "C" int me_ba_wait_out_cov(me_ctx* c, me_ba_summary* s, double* cams, double* pts, double* cam_cov,
                                   double* pt_cov, int* cov_ok) {
+  return me_ba_wait_out_check(c, s, cams, pts, cam_cov, pt_cov, cov_ok, nullptr, nullptr);
+}
+
+extern "C" int me_ba_wait_out_check(me_ctx* c, me_ba_summary* s, double* cams, double* pts, double* cam_cov,
+                                    double* pt_cov, int* cov_ok, uint8_t* flags, int* check_ok) {
   me_range range_("me_ba_wait");
+  if (check_ok) *check_ok = 0;
   if (!c) return ME_ERR_INVALID;
   auto* Q = (AsyncQueue*)c->ba_async;
   AsyncSolve* A = nullptr;
@@ -924,6 +953,10 @@ extern "C" int me_ba_wait_out_cov(me_ctx* c, me_ba_summary* s, double* cams, dou
         if (pt_cov && A->cov == 2 && g.np) std::memcpy(pt_cov, h + ncam + 1, 8 * 9 * (size_t)g.np);
       }
     }
+  }
+  if (check_ok && rc == ME_OK && A->check && A->sum.termination != 2) {  // the check's flags, from the same staging
+    *check_ok = 1;
+    if (flags && A->P.g.np) std::memcpy(flags, (const char*)A->P.host + A->P.check_off, (size_t)A->P.g.np);
   }
   hipEventDestroy(A->ev);
   A->ev = nullptr;
@@ -978,6 +1011,8 @@ extern "C" int me_ba_reserve(me_ctx* c, int n_cams, int n_pts, int n_obs, int ob
     ME_TRY(plan_build(c, &p, &o, P, kCovSet));
     CovOut out;
     ME_TRY(cov_out(c, P.g, out));
+    void* d;  // and the residual check's outputs (a host problem's chi2 | flags)
+    ME_TRY(me_scratch(c, kCheckOutSlot, 9 * (size_t)std::max(n_pts, 1) + 8, &d));
   }
   Plan P;  // and the synchronous one
   P.reserve_only = true;
@@ -1008,6 +1043,9 @@ extern "C" int me_vo_ba_chain(me_ctx* c, double* cams, int n_cams, double* pts, 
 extern "C" int me_vo_window_submit(me_ctx* c, const me_vo_window* w, me_ba_problem* p, const me_ba_options* o) {
   me_range range_("me_vo_window_submit");
   if (!c || !w || !p || !o) return ME_ERR_INVALID;
+  if (w->check)  // (refused before anything is queued)
+    if (const char* why = me_ba_point_check_check(w->check))
+      return me_set_error(c, ME_ERR_INVALID, "me_vo_window_submit: check: %s", why);
   ME_HIP(c, hipSetDevice(c->device));
   if (w->stage_bytes) ME_HIP(c, hipMemcpyAsync(w->dev, w->stage, w->stage_bytes, hipMemcpyHostToDevice, c->stream));
   if (w->chain)
@@ -1016,7 +1054,7 @@ extern "C" int me_vo_window_submit(me_ctx* c, const me_vo_window* w, me_ba_probl
   // (the problem's index arrays are the caller's device buffers, filled here)
   ME_TRY(me_ba_window_indices(c, w->frame, w->ids, p->n_obs, w->first_frame, w->win_ids, p->n_pts,
                               const_cast<int32_t*>(p->cam_idx), const_cast<int32_t*>(p->pt_idx)));
-  return solve_async_impl(c, p, o, true, w->cov == 1 || w->cov == 2 ? w->cov : 0);
+  return solve_async_impl(c, p, o, true, w->cov == 1 || w->cov == 2 ? w->cov : 0, w->check);
 }
 
 extern "C" void me_ba_default_options(me_ba_options* o) {
@@ -1280,6 +1318,42 @@ extern "C" int me_ba_covariance_full(me_ctx* c, const me_ba_problem* p, double* 
     if (cam_cov) std::memcpy(cam_cov, h, 8 * (size_t)ncam);
     if (pts) std::memcpy(pt_cov, h + ncam + 1, 8 * (size_t)npt);
   }
+  return ME_OK;
+}
+
+extern "C" int me_ba_point_check(me_ctx* c, const me_ba_problem* p, const me_ba_point_check_params* params, double* chi2,
+                                 uint8_t* flags, int* n_flagged) {
+  me_range range_("me_ba_point_check");
+  if (!c || !p || !flags) return ME_ERR_INVALID;
+  me_ba_point_check_params prm;
+  me_ba_point_check_default_params(&prm);
+  if (params) prm = *params;
+  if (const char* why = me_ba_point_check_check(&prm)) return me_set_error(c, ME_ERR_INVALID, "me_ba_point_check: %s", why);
+  const bool dev = p->mem == ME_DEVICE;
+  ME_CHECK(c, !dev || !n_flagged, "me_ba_point_check: n_flagged is a host result (NULL for a device-resident problem)");
+  ME_HIP(c, hipSetDevice(c->device));
+  me_ba_options o;
+  me_ba_default_options(&o);
+  Plan P;
+  P.cov = true;  // (as the covariance: a device-resident problem's plan in set kCovSet, no drain, no staging)
+  ME_TRY(plan_build(c, p, &o, P, dev ? kCovSet : 0));
+  const Geo& g = P.g;
+  if (dev) return me_ba_check_launch(c, g, P.b, p->cams, p->pts, &prm, chi2, flags);
+  if (n_flagged) *n_flagged = 0;
+  if (g.np == 0) {
+    ME_HIP(c, hipStreamSynchronize(c->stream));  // (the plan reads the caller's staging)
+    return ME_OK;
+  }
+  void* d;
+  ME_TRY(me_scratch(c, kCheckOutSlot, 9 * (size_t)g.np + 8, &d));
+  double* dchi2 = (double*)d;
+  uint8_t* dflags = (uint8_t*)(dchi2 + g.np);
+  ME_TRY(me_ba_check_launch(c, g, P.b, P.b.cams[0], P.b.pts[0], &prm, dchi2, dflags));
+  if (chi2) ME_HIP(c, hipMemcpyAsync(chi2, dchi2, 8 * (size_t)g.np, hipMemcpyDeviceToHost, c->stream));
+  ME_HIP(c, hipMemcpyAsync(flags, dflags, (size_t)g.np, hipMemcpyDeviceToHost, c->stream));
+  ME_HIP(c, hipStreamSynchronize(c->stream));
+  if (n_flagged)
+    for (int i = 0; i < g.np; ++i) *n_flagged += flags[i] != 0;
   return ME_OK;
 }
 

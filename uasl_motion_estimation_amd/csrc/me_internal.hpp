@@ -127,6 +127,18 @@ const char* me_frame_pose_check(const me_frame_pose_params* p);
 // me_kf_update's parameter checks (keyframe.hip): NULL, or the message naming the argument.
 const char* me_kf_check(const me_kf_params* p);
 
+// me_ba_point_check's parameter checks (ba_check.hip): NULL, or the message naming the argument.
+const char* me_ba_point_check_check(const me_ba_point_check_params* p);
+// The per-landmark residual check (ba_check.hip) of a built BA plan (ba.hip: its geometry and buffers, the CSR by
+// point) at the cameras / points given, queued on the ctx stream: chi2 (np doubles, or null) and flags (np bytes),
+// device memory.  Timed in the ME_KT_BA_CHECK family.
+namespace ba {
+struct Geo;
+struct Bufs;
+}  // namespace ba
+int me_ba_check_launch(me_ctx* ctx, const ba::Geo& g, const ba::Bufs& b, const double* cams, const double* pts,
+                       const me_ba_point_check_params* p, double* chi2, uint8_t* flags);
+
 // roctx range (rocprofv3 --marker-trace) around an entry point's host work.
 struct me_range {
   explicit me_range(const char* name);

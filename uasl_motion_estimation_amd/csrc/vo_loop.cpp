@@ -56,6 +56,15 @@ struct me_vo_loop {
   int cov_mode = 0;
   std::map<int, std::vector<double>> pose_cov;
   std::map<int64_t, std::vector<double>> track_cov;
+  // the residual check behind every window solve (me_vo_loop_set_track_check) and what it flagged so far
+  bool track_check = false;
+  me_ba_point_check_params check_params{};
+  struct Flagged {
+    int32_t t;
+    int64_t id;
+    uint8_t flags;
+  };
+  std::vector<Flagged> flagged;
   bool klt_predict = false;  // the tracker starts at each landmark's predicted pixel (me_vo_loop_set_klt_predict)
   long n_pushed = 0;
   Camera cam;
@@ -164,7 +173,7 @@ struct me_vo_loop {
       return env.fail(ME_ERR_STATE, "track IDs exceed the device window's int32");
     std::vector<Pose> cams;
     for (int fr = f0; fr <= t; ++fr) cams.push_back(poses[fr]);
-    VL_TRY(win.submit(f0, wid32, Xw, cams, chain, cov_mode, &rec->nobs), "window");
+    VL_TRY(win.submit(f0, wid32, Xw, cams, chain, cov_mode, track_check ? &check_params : nullptr, &rec->nobs), "window");
     *has = true;
     return ME_OK;
   }
@@ -176,8 +185,12 @@ struct me_vo_loop {
     }
     std::vector<double> c, p, ccov, pcov;
     me_ba_summary s;
-    int cov_ok = 0;
-    if (cov_mode)
+    std::vector<uint8_t> flags;
+    int cov_ok = 0, check_ok = 0;
+    if (track_check)
+      VL_TRY(win.result(c, p, s, cov_mode ? &ccov : nullptr, cov_mode ? &pcov : nullptr, cov_mode ? &cov_ok : nullptr,
+                        &flags, &check_ok), "BA result");
+    else if (cov_mode)
       VL_TRY(win.result(c, p, s, &ccov, &pcov, &cov_ok), "BA result");
     else
       VL_TRY(win.result(c, p, s), "BA result");
@@ -210,6 +223,15 @@ struct me_vo_loop {
           }
           track_cov[ba.wids[i]] = b;
         }
+    }
+    if (track_check && s.status == 2 && check_ok) {  // the flagged tracks still in the table are tracked no further
+      std::vector<int64_t> rows;
+      for (size_t i = 0; i < m; ++i)
+        if (live[i] && flags[i]) {
+          rows.push_back(j[i]);
+          flagged.push_back(Flagged{(int32_t)ba.t, ba.wids[i], flags[i]});
+        }
+      tab.deactivate(rows);
     }
     *nwp = (int)ba.wids.size();
     *nwo = ba.nobs;
@@ -581,6 +603,30 @@ int me_vo_loop_set_covariance(me_vo_loop* v, const me_vo_cov_params* p) {
   if (!v) return ME_ERR_INVALID;
   if (started(v, "me_vo_loop_set_covariance: the window covariance is set before the first frame")) return ME_ERR_STATE;
   v->cov_mode = p ? (p->landmarks ? 2 : 1) : 0;
+  return ME_OK;
+}
+
+int me_vo_loop_set_track_check(me_vo_loop* v, const me_ba_point_check_params* p) {
+  if (!v) return ME_ERR_INVALID;
+  if (p)
+    if (const char* why = me_ba_point_check_check(p)) {
+      v->env.err = std::string("me_vo_loop_set_track_check: ") + why;
+      return ME_ERR_INVALID;
+    }
+  if (started(v, "me_vo_loop_set_track_check: the residual check is set before the first frame")) return ME_ERR_STATE;
+  v->track_check = p != nullptr;
+  if (p) v->check_params = *p;
+  return ME_OK;
+}
+
+int me_vo_loop_flagged(me_vo_loop* v, int32_t* ts, int64_t* ids, uint8_t* flags, int cap, int* n) {
+  if (!v || !n) return ME_ERR_INVALID;
+  *n = (int)v->flagged.size();
+  for (int i = 0; i < std::min(cap, *n); ++i) {
+    if (ts) ts[i] = v->flagged[(size_t)i].t;
+    if (ids) ids[i] = v->flagged[(size_t)i].id;
+    if (flags) flags[i] = v->flagged[(size_t)i].flags;
+  }
   return ME_OK;
 }
 

@@ -36,6 +36,7 @@ struct WindowQueue {
     me_ba_problem p{};
     me_ba_options o{};
     me_vo_window w{};
+    me_ba_point_check_params chk{};  // w.check points here when the residual check is queued
     int nc = 0, npts = 0;
     const int32_t* dev_ids = nullptr;
     int n_ids = 0;
@@ -150,9 +151,10 @@ struct WindowQueue {
     wend += n;
     return ME_OK;
   }
-  // cov: the window covariance mode handed to the solve (me_vo_window.cov)
+  // cov: the window covariance mode handed to the solve (me_vo_window.cov); check: the residual check's parameters
+  // (me_vo_window.check), null: none
   int submit(int f0, const std::vector<int32_t>& win_ids, const std::vector<double>& Xw, const std::vector<Pose>& cams,
-             const Chain* chain, int cov, int* n_obs_out) {
+             const Chain* chain, int cov, const me_ba_point_check_params* check, int* n_obs_out) {
     const me_vo_loop_config& cfg = env.cfg;
     VL_TRY(join_enqueue(), "window");
     const long off0 = wfrm[f0].first;
@@ -192,6 +194,10 @@ struct WindowQueue {
     w.ids = st.id(ws, off0);
     w.first_frame = f0;
     w.cov = cov;
+    if (check) {
+      q->chk = *check;
+      w.check = &q->chk;
+    }
     me_ba_problem& p = q->p;
     p = me_ba_problem{};
     p.n_cams = nc;
@@ -229,9 +235,11 @@ struct WindowQueue {
     *n_obs_out = (int)n_obs;
     return ME_OK;
   }
-  // ccov / pcov / cov_ok (all three or none): the window's covariance, read back with the result
+  // ccov / pcov / cov_ok (all three or none): the window's covariance, read back with the result; flags / check_ok
+  // (both or none): the residual check's flags, one per window point
   int result(std::vector<double>& cams, std::vector<double>& pts, me_ba_summary& s, std::vector<double>* ccov = nullptr,
-             std::vector<double>* pcov = nullptr, int* cov_ok = nullptr) {
+             std::vector<double>* pcov = nullptr, int* cov_ok = nullptr, std::vector<uint8_t>* flags = nullptr,
+             int* check_ok = nullptr) {
     me_ctx* ctx = env.ctx;
     if (baq.empty()) return env.fail(ME_ERR_STATE, "no window solve queued");
     std::unique_ptr<QSolve> q = std::move(baq.front());
@@ -242,6 +250,18 @@ struct WindowQueue {
     }
     cams.assign(6 * (size_t)q->nc, 0.0);
     pts.assign(3 * (size_t)q->npts, 0.0);
+    if (check_ok) {
+      flags->assign((size_t)q->npts, 0);
+      if (cov_ok) {
+        ccov->assign(36 * (size_t)q->nc, 0.0);
+        pcov->assign(9 * (size_t)q->npts, 0.0);
+      }
+      VL_TRY(env.timed_wait(4, [&] {
+               return me_ba_wait_out_check(ctx, &s, cams.data(), pts.data(), cov_ok ? ccov->data() : nullptr,
+                                           cov_ok ? pcov->data() : nullptr, cov_ok, flags->data(), check_ok);
+             }), "me_ba_wait_out");
+      return ME_OK;
+    }
     if (cov_ok) {
       ccov->assign(36 * (size_t)q->nc, 0.0);
       pcov->assign(9 * (size_t)q->npts, 0.0);

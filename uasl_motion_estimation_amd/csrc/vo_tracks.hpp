@@ -219,6 +219,12 @@ struct TrackTable {
     }
   }
 
+  // The residual check's verdict on a solved window (me_vo_loop_set_track_check): the rows given are tracked no
+  // further.  They keep their observations and their place in the windows that hold them, and leave by the pops.
+  void deactivate(const std::vector<int64_t>& rows) {
+    for (int64_t r : rows) active[(size_t)r] = 0;
+  }
+
   // kf_seed: the active tracks' left positions in keyframe t, in table order (the order the next tracker upload
   // has), and with want_xr their x_r there
   void seeded(int t, bool want_xr, std::vector<float>& ref, std::vector<float>& xr) const {

@@ -674,6 +674,34 @@ class DeviceBAProblem:
             self.ctx.d2h(pt, self.d["cov_pt"])
         return int(ok[0]), cam, pt
 
+    def point_check_async(self, params=None) -> None:
+        """Queue the residual check of the device-resident cams / pts on the
+        ctx stream (me_ba_point_check, ME_DEVICE form).  Its device outputs
+        (check_chi2, check_flags in self.d) are created on first use; the
+        check writes every landmark's entry."""
+        from .track_check import TrackCheck
+
+        n = max(self.n_pts, 1)
+        if "check_chi2" not in self.d:
+            for k, nb in dict(check_chi2=8 * n, check_flags=max(n, 16)).items():
+                self.d[k] = self.ctx.malloc(nb)
+                self._blocks.append(self.d[k])
+        p = self.struct()
+        prm = (params or TrackCheck()).to_c()
+        self.ctx.check(self.ctx.lib.me_ba_point_check(self.ctx.h, byref(p), byref(prm), self.d["check_chi2"],
+                                                      self.d["check_flags"], None), "me_ba_point_check")
+
+    def point_check_read(self):
+        """(chi2, flags) of the last point_check_async, as the device holds
+        them (waits for the ctx stream)."""
+        self.ctx.synchronize()
+        chi2 = np.zeros(self.n_pts)
+        flags = np.zeros(self.n_pts, np.uint8)
+        if self.n_pts:
+            self.ctx.d2h(chi2, self.d["check_chi2"])
+            self.ctx.d2h(flags, self.d["check_flags"])
+        return chi2, flags
+
     def download(self):
         cams = np.zeros((self.n_cams, 6))
         pts = np.zeros((self.n_pts, 3))
@@ -953,6 +981,25 @@ def ba_covariance_full(bp, ctx: Context | None = None, landmarks: bool = True):
     if not ok.value:
         return None
     return cam.reshape(-1, 6, 6), (pt.reshape(-1, 3, 3) if landmarks else None)
+
+
+def ba_point_check(bp, params=None, ctx: Context | None = None):
+    """Per-landmark residual check at the problem's current parameters
+    (me_ba_point_check; track_check.point_check_ref restates it): (chi2
+    (n_pts,) float64, flags (n_pts,) uint8, number of landmarks flagged).
+    ``params``: a track_check.TrackCheck, None for the defaults."""
+    from .track_check import TrackCheck
+
+    ctx = ctx or default_context()
+    keep = []
+    p, _, _ = ba_struct(bp, keep)
+    prm = (params or TrackCheck()).to_c()
+    chi2 = np.zeros(len(bp.pts))
+    flags = np.zeros(len(bp.pts), np.uint8)
+    n = c_int(0)
+    ctx.check(ctx.lib.me_ba_point_check(ctx.h, byref(p), byref(prm), chi2.ctypes.data, flags.ctypes.data,
+                                        ctypes.addressof(n)), "me_ba_point_check")
+    return chi2, flags, n.value
 
 
 def ba_reduced_system(bp, radius: float = 1e4, ctx: Context | None = None):

@@ -134,8 +134,14 @@ class PipelineConfig:
     keyframe_select: "KeyframeSelect | None" = None  # keyframe.KeyframeSelect: push() takes camera frames, picks keyframes
     frame_pose: "FramePose | None" = None  # frame_pose.FramePose: every pushed frame gets a pose relative to the last keyframe
     covariance: "WindowCovariance | None" = None  # ba_cov.WindowCovariance: every window's covariance (pose_cov / track_cov)
+    track_check: "TrackCheck | None" = None  # track_check.TrackCheck: tracks that do not fit their solved window are dropped
 
     def __post_init__(self):
+        if self.track_check is not None:
+            from .track_check import TrackCheck
+
+            if not isinstance(self.track_check, TrackCheck):
+                raise ValueError("track_check must be a track_check.TrackCheck or None")
         if self.keyframe_select is not None:
             from .keyframe import KeyframeSelect
 
@@ -442,6 +448,9 @@ class Backend:
     klt_predict = False  # PipelineConfig.klt_predict of the loop's configuration (True: klt_submit gets a guess)
     cov_mode = 0  # PipelineConfig.covariance: 0 off, 1 camera blocks, 2 also landmark blocks
     last_cov = None  # a backend that computes the window covariance itself: (ok, cam_cov, pt_cov) of the last ba_result
+    track_check = None  # PipelineConfig.track_check of the loop's configuration (None: no residual check)
+    last_check = None  # a backend that runs the check itself behind the solve: (ok, flags) of the last ba_result
+    check_log = None  # host backends: (t, track IDs, chi2, flags) of every window checked (point_check_ref), in order
     rectifier = None  # PipelineConfig.rectify of the loop's configuration (None: the images come rectified)
     rectifies = False  # True: frame_images takes raw images and warps them itself (on the device)
     equaliser = None  # PipelineConfig.equalise of the loop's configuration (None: the images are used as they come)
@@ -663,6 +672,29 @@ class Backend:
     def ba_result(self):
         r, self._ba_res = self._ba_res, None
         return r
+
+    def point_check_host(self, t, wids, bp):
+        """The residual check of window t (track IDs wids) on the host, for a
+        backend that did not run it behind the solve: point_check_ref on this
+        backend's own residuals (ba_residuals) of the host problem bp, which
+        holds the solved cams / pts.  The backend owns the log: (t, track IDs,
+        chi2, flags) of every window goes into check_log.  Returns the flags."""
+        from .track_check import point_check_problem
+
+        chi2, flags = point_check_problem(bp, self.ba_residuals, self.track_check)
+        if self.check_log is None:
+            self.check_log = []
+        self.check_log.append((int(t), np.asarray(wids).copy(), chi2, flags))
+        return flags
+
+    def ba_residuals(self, bp):
+        """Sigma-scaled residuals (n_obs, D) of a host problem at its
+        parameters, for the residual check of a backend without a device
+        (point_check_host): the numpy restatement unless the
+        backend has residuals of its own."""
+        from .ba_cov import stereo_jacobians
+
+        return stereo_jacobians(bp)[0]
 
     # ---- device-resident BA window (GPU): observations appended per keyframe
     device_window = False
@@ -1482,6 +1514,10 @@ class GPUBackend(Backend):
         o, f, i = self._wview(self._wcur)
         w.win_ids, w.frame, w.ids, w.first_frame = d + o_ids, f + 4 * off0, i + 4 * off0, f0
         w.cov = int(self.cov_mode)  # (queued behind the solve, read back with its result: ba_result)
+        chk = None
+        if self.track_check is not None:  # the residual check, likewise
+            chk = self.track_check.to_c()
+            w.check = ctypes.addressof(chk)
         p = BAProblemC()
         p.n_cams, p.n_pts, p.n_obs = nc, npts, n_obs
         p.cams = ctypes.cast(d, ctypes.POINTER(ctypes.c_double))
@@ -1518,7 +1554,7 @@ class GPUBackend(Backend):
             fut = self._ba_fut = self._ba_pool.submit(enqueue)
         else:
             enqueue()
-        self._baq.append(("dev", p, opt, w, nc, npts, (d + o_ids, npts), fut))
+        self._baq.append(("dev", p, opt, w, nc, npts, (d + o_ids, npts), fut, chk))
         return n_obs
 
     def _join_enqueue(self):
@@ -1554,14 +1590,25 @@ class GPUBackend(Backend):
         s = BASummaryC()
         c = self.ctx
         if rec[0] == "dev":
-            _, p, o, w, nc, npts, _, fut = rec
+            _, p, o, w, nc, npts, _, fut, chk = rec
             if fut is not None:  # this window's own queueing (a newer one's may run on beside the wait)
                 fut.result()
                 if fut is self._ba_fut:
                     self._ba_fut = None
             cams = np.empty((nc, 6), np.float64)
             pts = np.empty((npts, 3), np.float64)
-            if self.cov_mode:  # the window's covariance from the solve's own staging: no further wait
+            if chk is not None:  # the check's flags (and the covariance) from the solve's own staging: no further wait
+                ccov, pcov, cok = np.zeros((nc, 6, 6)), np.zeros((npts, 3, 3)), ctypes.c_int(0)
+                flags, fok = np.zeros(npts, np.uint8), ctypes.c_int(0)
+                cov = self.cov_mode != 0
+                c.check(c.lib.me_ba_wait_out_check(c.h, ctypes.byref(s), cams.ctypes.data, pts.ctypes.data,
+                                                   ccov.ctypes.data if cov else None, pcov.ctypes.data if cov else None,
+                                                   ctypes.addressof(cok) if cov else None, flags.ctypes.data,
+                                                   ctypes.addressof(fok)), "me_ba_wait_out")
+                if cov:
+                    self.last_cov = (cok.value, ccov, pcov)
+                self.last_check = (fok.value, flags)
+            elif self.cov_mode:  # the window's covariance from the solve's own staging: no further wait
                 ccov, pcov, cok = np.zeros((nc, 6, 6)), np.zeros((npts, 3, 3)), ctypes.c_int(0)
                 c.check(c.lib.me_ba_wait_out_cov(c.h, ctypes.byref(s), cams.ctypes.data, pts.ctypes.data,
                                                  ccov.ctypes.data, pcov.ctypes.data, ctypes.addressof(cok)),
@@ -1614,6 +1661,8 @@ class WindowedStereoVO:
         self.be.match_lr_max = float(cfg.match_lr_max)
         self.be.klt_predict = bool(cfg.klt_predict)
         self.be.cov_mode = 0 if cfg.covariance is None else (2 if cfg.covariance.landmarks else 1)
+        self.be.track_check = cfg.track_check
+        self._flagged = []    # (window keyframe, track ID, flags) of every track the residual check dropped, in order
         self._pose_cov = {}   # keyframe t -> (ok, 6 x 6): the last camera's block of t's own window
         self._track_cov = {}  # live track ID -> (ok, 3 x 3): the block of the latest window that held it
         self.be.rectifier = cfg.rectify
@@ -2084,8 +2133,9 @@ class WindowedStereoVO:
             return (t, f0, self.ids[upts].copy(), n_obs, upts, self._gen)
         bp = self.ba_problem(t, f0, upts)
         self._wait(self.be.ba_submit, bp, cfg.ba_iters)
-        # (with the covariance switch the host problem is kept: its covariance is taken at the solved cams / pts)
-        return (t, f0, self.ids[upts].copy(), len(bp.obs), upts, self._gen) + ((bp,) if self.be.cov_mode else ())
+        # (with the covariance or the check switch the host problem is kept: both are taken at the solved cams / pts)
+        keep = self.be.cov_mode or self.be.track_check is not None
+        return (t, f0, self.ids[upts].copy(), len(bp.obs), upts, self._gen) + ((bp,) if keep else ())
 
     def ba_problem(self, t, f0, upts):
         """The window [f0, t]'s BA problem on the host (host-path backends;
@@ -2121,6 +2171,7 @@ class WindowedStereoVO:
             return 0, 0, {"iterations": 0, "final_cost": float("nan")}
         t, f0, wids, nobs, upts, gen = ba[:6]
         self.be.last_cov = None
+        self.be.last_check = None
         c, p, s = self._wait(self.be.ba_result)
         # the window's tracks now (a pop may have compacted the table since the submit -- its index map;
         # a track popped out of the table, seen only in the window's first keyframe, needs no landmark)
@@ -2147,7 +2198,40 @@ class WindowedStereoVO:
             self.X[j[live]] = np.asarray(p)[live]
         if self.be.cov_mode:  # (read only: nothing above depends on it)
             self._record_cov(ba, c, p, s, live)
+        if self.be.track_check is not None and s.get("status", 2) == 2:
+            flags = self._check_flags(ba, c, p)
+            if flags is not None:  # the flagged tracks still in the table are tracked no further
+                hit = live & (flags != 0)
+                self._flagged += [(int(t), int(i), int(f)) for i, f in zip(wids[hit], flags[hit])]
+                self.deactivate(j[hit])
         return len(wids), nobs, s
+
+    def deactivate(self, rows):
+        """The residual check's verdict on a solved window: the table rows
+        given are tracked no further (TrackTable::deactivate).  They keep their
+        observations and their place in the windows that hold them, and leave
+        by the pops."""
+        self.active[np.asarray(rows, np.int64)] = False
+
+    def _check_flags(self, ba, c, p):
+        """The residual check's flags of a solved window, one per window
+        point: from the backend when it ran the check behind the solve (GPU,
+        device-resident window; None when that gave none), else the backend's
+        host restatement (Backend.point_check_host) of the host problem at the
+        solved cams / pts."""
+        if self.be.last_check is not None:
+            ok, flags = self.be.last_check
+            return flags if ok else None
+        if len(ba) <= 6:
+            return None
+        bp = ba[6].copy()
+        bp.cams, bp.pts = np.asarray(c, np.float64), np.asarray(p, np.float64)
+        return self.be.point_check_host(int(ba[0]), ba[2], bp)
+
+    def flagged(self):
+        """[(window keyframe, track ID, flags)] of every track the residual
+        check dropped so far, in the order applied (me_vo_loop_flagged)."""
+        return list(self._flagged)
 
     def _record_cov(self, ba, c, p, s, live):
         """The window's covariance beside its result: from the backend when it
@@ -2306,6 +2390,9 @@ class NativeStereoVO:
                 self._check(self.lib.me_vo_loop_set_motion_gate(self.h, ctypes.byref(gp)), "me_vo_loop_set_motion_gate")
             if cfg.klt_predict:
                 self._check(self.lib.me_vo_loop_set_klt_predict(self.h, 1), "me_vo_loop_set_klt_predict")
+            if cfg.track_check is not None:
+                tc = cfg.track_check.to_c()
+                self._check(self.lib.me_vo_loop_set_track_check(self.h, ctypes.byref(tc)), "me_vo_loop_set_track_check")
             if cfg.covariance is not None:
                 from ._lib import VOCovParamsC
 
@@ -2590,6 +2677,18 @@ class NativeStereoVO:
         self._check(self.lib.me_vo_loop_pose_covs(self.h, ts.ctypes.data, cov.ctypes.data, ok.ctypes.data, m,
                                                   ctypes.byref(n)), "pose_covs")
         return ts, cov, ok.astype(bool)
+
+    def flagged(self):
+        """WindowedStereoVO.flagged (me_vo_loop_flagged)."""
+        import ctypes
+
+        n = ctypes.c_int(0)
+        self._check(self.lib.me_vo_loop_flagged(self.h, None, None, None, 0, ctypes.byref(n)), "flagged")
+        m = n.value
+        ts, ids, fl = np.zeros(m, np.int32), np.zeros(m, np.int64), np.zeros(m, np.uint8)
+        self._check(self.lib.me_vo_loop_flagged(self.h, ts.ctypes.data, ids.ctypes.data, fl.ctypes.data, m,
+                                                ctypes.byref(n)), "flagged")
+        return [(int(a), int(b), int(c)) for a, b, c in zip(ts, ids, fl)]
 
     def pose_cov(self, t: int):
         """WindowedStereoVO.pose_cov (me_vo_loop_pose_covs)."""
